@@ -1,7 +1,14 @@
 #!/usr/bin/env python3
 """Benchmark of the hot path: Mray/s (primary + secondary) at 1024x768, depth 4 (BASELINE.json).
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--config C2|C3|C4|C5|ref|readme] [--no-cpu]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--config C2|C3|C4|C5|ref|readme]
+                  [--dump-outputs DIR] [--full [--no-cpu]]
+
+A plain run sets up, warms up, times the K steps of the headline's path, writes the last
+step's frame with --dump-outputs, and prints the line (metric, value, ms_per_step, config).
+Everything else below — the event pass and roofline, the last-frame checks, the other paths at
+the same N, the tiled, shipped, README, C3 / C5 / per-frame-launch and C-ABI legs, the PMC
+traffic and the CPU baseline — runs only with --full.
 
 Every frame has its own UBO: the camera walks like the reference's interactive loop with W and
 D held (processInput + updateUniformBuffer, main.cpp:391-403, 2165-2179), cycling through
@@ -14,7 +21,7 @@ profiles/r04l_settle.jsonl).  The timed region itself holds exactly K full steps
 
 * N = 1: one step = one frame.  The value is the native frame loop (trt_render_frames: plain
   frames go out as multi-frame launches) — `path` in the line says which path produced it; the
-  N > 1 path at one rank is reported beside it (`tiled_1gpu`) as the base of the scaling curve.
+  N > 1 path at one rank is reported beside it (`tiled_1gpu`, --full) as the base of the scaling curve.
 * N > 1 (one process per GPU under torch.distributed.run): one step = N frames, EACH row-tiled
   over all N GPUs (interleaved 8-row bands) and gathered over RCCL to its own root, rank i % N
   (trt_render_multi_frames: per-frame rotating roots, so every device's xGMI links ingest at
@@ -22,7 +29,7 @@ profiles/r04l_settle.jsonl).  The timed region itself holds exactly K full steps
   form (one frame per step over all N GPUs) and the frame-per-GPU form (no collective) are
   reported beside it.
 
-Rank 0 prints ONE JSON line.  Extra keys: `tiled_frame` (BASELINE configs[3]: a 3840x2160
+Rank 0 prints ONE JSON line.  Extra keys with --full: `tiled_frame` (BASELINE configs[3]: a 3840x2160
 ~100k-triangle frame row-tiled over the N GPUs and gathered on rank 0 over RCCL, hash-checked
 against the 1-GPU frame and the committed hash), `shipped_frame` (the reference's own default
 frame, config.hpp:97-101 at MAX_DEPTH 20), `readme_frame` (the scene of the reference's only
@@ -62,7 +69,14 @@ def parse():
     ap.add_argument("--steps", type=int, default=1000)
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--config", default="C2", choices=["C2", "C3", "C4", "C5", "ref", "readme"])
-    ap.add_argument("--no-cpu", action="store_true", help="skip the CPU oracle baseline")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline: the per-launch event pass, the last-frame checks, the roofline and "
+                         "its PMC traffic, the tiled legs, the extra scenes and configs, the C-ABI host and the "
+                         "CPU baseline (a plain run times the headline's steps and nothing else)")
+    ap.add_argument("--dump-outputs", type=Path, default=None, metavar="DIR",
+                    help="after the timed steps, write the frame the timed path rendered in its last step as "
+                         "DIR/last_frame.npy (height x width x RGBA, float32)")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip the CPU oracle baseline")
     ap.add_argument("--cpu-seconds", type=float, default=10.0, help="CPU baseline time budget per thread count")
     ap.add_argument("--inflight", type=int, default=0,
                     help="frames in flight (trt_set_frames_in_flight: 0 = auto; the reference's is 2)")
@@ -336,9 +350,21 @@ def rays_of(st: dict) -> int:
     return int(st["primary_rays"] + st["secondary_rays"])
 
 
-def frame_loop(dev: int, scene, frames: int, warmup: int, args, g: Group | None = None, check_last: bool = True):
-    """trt_render_frames of `scene` on one GPU over the camera walk: wall time, per-frame launch
-    times, the walk's counts, and whether the last timed frame equals trt_render of its UBO."""
+def dump_frame(outdir: Path, frame8) -> None:
+    """--dump-outputs: one RGBA8 device frame of the timed loop's ring as DIR/last_frame.npy
+    (float32, 0..255: 12.6 MB at 1024x768)."""
+    import numpy as np
+
+    outdir.mkdir(parents=True, exist_ok=True)
+    np.save(outdir / "last_frame.npy", frame8.cpu().numpy().astype(np.float32))
+
+
+def frame_loop(dev: int, scene, frames: int, warmup: int, args, g: Group | None = None, check_last: bool = True,
+               events: bool = True, dump: Path | None = None):
+    """trt_render_frames of `scene` on one GPU over the camera walk: wall time and the walk's
+    counts; with `events` a second, untimed pass for the per-frame launch times; with
+    `check_last` whether the last timed frame equals trt_render of its UBO; with `dump` that
+    frame written out (dump_frame)."""
     import numpy as np
     import torch
 
@@ -373,21 +399,25 @@ def frame_loop(dev: int, scene, frames: int, warmup: int, args, g: Group | None 
                 call()
 
         elapsed = timed(g or Group(1, 0), run)
-        # the same loop again with HIP events around every launch (outside the timed region):
-        # the device time per frame of the launches
-        ms, nf = [], []
-        for (_, n), u in zip(chunks, ubo_chunks):
-            nt = r.render_frames(p, out8, n, ubos=u, frame_stride=fb, timing=True)
-            ms.append(r.frame_times(nt))
-            nf.append(r.launch_frames())
-        ms = np.concatenate(ms)
-        nf = np.concatenate(nf).astype(np.float64)
-        kernel_ms_per_frame = float((ms * nf).sum() / nf.sum())  # launch spans / frames
-        launches = int(len(nf))
+        last = frames - 1
+        if dump is not None:
+            dump_frame(dump, out8[last % ring])
+        kernel_ms_per_frame = launches = None
+        if events:
+            # the same loop again with HIP events around every launch (outside the timed
+            # region): the device time per frame of the launches
+            ms, nf = [], []
+            for (_, n), u in zip(chunks, ubo_chunks):
+                nt = r.render_frames(p, out8, n, ubos=u, frame_stride=fb, timing=True)
+                ms.append(r.frame_times(nt))
+                nf.append(r.launch_frames())
+            ms = np.concatenate(ms)
+            nf = np.concatenate(nf).astype(np.float64)
+            kernel_ms_per_frame = float((ms * nf).sum() / nf.sum())  # launch spans / frames
+            launches = int(len(nf))
         torch.cuda.synchronize()
         ok = None
         if check_last:
-            last = frames - 1
             got = out8[last % ring].cpu().numpy()
             r.set_stream(None)
             r.update_ubo(ubos[last])
@@ -407,10 +437,12 @@ def auto_per_gather(total: int, world: int, arg: int) -> int:
     return max(1, min(64, -(-total // 4)))  # >= 4 exchanges pipeline in the timed region
 
 
-def tiled_loop(g: Group, dev: int, multi, scene, frames: int, warmup: int, args, per_gather: int, root: int):
+def tiled_loop(g: Group, dev: int, multi, scene, frames: int, warmup: int, args, per_gather: int, root: int,
+               check: bool = True, dump: Path | None = None):
     """trt_render_multi_frames over all ranks along the camera walk: frame i row-tiled over the
     ranks and assembled on rank frame_root(i): (elapsed s, rays of all frames, walk mean stats,
-    last-frame check on every rank that rooted frames)."""
+    last-frame check on every rank that rooted frames, or None without `check`).  With `dump`,
+    rank 0 writes out the last frame it assembled (dump_frame)."""
     import numpy as np
     import torch
 
@@ -464,6 +496,10 @@ def tiled_loop(g: Group, dev: int, multi, scene, frames: int, warmup: int, args,
     multi.set_stream(0, None)
     # the last frame this rank assembled vs trt_render of its UBO on this GPU
     mine = [i for i in range(frames) if frame_root(i % ring, g.world, root) == g.rank]
+    if dump is not None and g.rank == 0 and mine:
+        dump_frame(dump, out[mine[-1] % ring])
+    if not check:
+        return elapsed, rays_total, mean, None
     ok = 1.0
     if mine:
         last = mine[-1]
@@ -812,38 +848,58 @@ def main():
     mesh = len(scene.models) > 0
     pixels = scene.width * scene.height
 
-    # Frame per GPU: the plain frame loop on every rank, no data-path collective (the N = 1
-    # value; at N > 1 the frame-per-GPU extra).  Also the live launch timing.
-    fl = frame_loop(dev, scene, K, args.warmup, args, g=g)
-    plain_value = g.sum(fl["rays_total"]) / fl["elapsed"] / 1e6
-    plain_ok = g.min(1.0 if fl["last_frame_ok"] else 0.0) > 0.5
+    # A plain run holds the headline's loop and nothing else: set up (with the counting passes
+    # that give the rays per frame), warm up, time the K steps, dump, print.  --full adds the
+    # event pass, the checks, the other paths and legs and the CPU baseline.
+    full = args.full
+    dump = args.dump_outputs
 
-    multi = MultiRenderer.for_rank(dev, world, rank, g.unique_id())
-    # the tiled loop: N frames per step (weak), each row-tiled over all N GPUs, rotating roots
+    # Frame per GPU: the plain frame loop on every rank, no data-path collective (the N = 1
+    # value; at N > 1 the frame-per-GPU extra of --full).  With --full also the live launch timing.
+    fl = plain_value = plain_ok = None
+    if full or not dist_mode:
+        fl = frame_loop(dev, scene, K, args.warmup, args, g=g, check_last=full, events=full,
+                        dump=None if dist_mode else dump)
+        plain_value = g.sum(fl["rays_total"]) / fl["elapsed"] / 1e6
+        if full:
+            plain_ok = g.min(1.0 if fl["last_frame_ok"] else 0.0) > 0.5
+
+    multi = tiled = None
     t_frames = K * world
     fpg = auto_per_gather(t_frames, world, args.frames_per_gather)
-    el_t, rays_t, mean_t, tiled_ok = tiled_loop(g, dev, multi, scene, t_frames, args.warmup, args, fpg, ROOT_ROTATE)
-    tiled_value = rays_t / el_t / 1e6
-    tiled = {
-        "value": round(tiled_value, 3), "unit": "Mray/s", "ms_per_step": round(el_t / K * 1e3, 5),
-        "frames": t_frames, "frames_per_gather": fpg, "last_frames_match_trt_render": tiled_ok,
-        "path": "trt_render_multi_frames: every frame row-tiled over all ranks in interleaved "
-                f"{args.band_rows}-row bands, RCCL exchange of {fpg} frames per op to per-frame rotating roots "
-                "(frame i -> rank i % N)" + (" — 1 rank: every band traced in place, nothing travels"
-                                             if world == 1 else ""),
-    }
+    if full or dist_mode:
+        multi = MultiRenderer.for_rank(dev, world, rank, g.unique_id())
+        # the tiled loop: N frames per step (weak), each row-tiled over all N GPUs, rotating roots
+        el_t, rays_t, mean_t, tiled_ok = tiled_loop(g, dev, multi, scene, t_frames, args.warmup, args, fpg,
+                                                    ROOT_ROTATE, check=full, dump=dump if dist_mode else None)
+        tiled_value = rays_t / el_t / 1e6
+        tiled = {
+            "value": round(tiled_value, 3), "unit": "Mray/s", "ms_per_step": round(el_t / K * 1e3, 5),
+            "frames": t_frames, "frames_per_gather": fpg, "last_frames_match_trt_render": tiled_ok,
+            "path": "trt_render_multi_frames: every frame row-tiled over all ranks in interleaved "
+                    f"{args.band_rows}-row bands, RCCL exchange of {fpg} frames per op to per-frame rotating roots "
+                    "(frame i -> rank i % N)" + (" — 1 rank: every band traced in place, nothing travels"
+                                                 if world == 1 else ""),
+        }
+        if not full:
+            del tiled["last_frames_match_trt_render"]
     extra = {}
     if not dist_mode:
         value, ms_per_step, scaling = plain_value, fl["elapsed"] / K * 1e3, "weak"
         path = "trt_render_frames (plain frame loop, multi-frame launches)"
         parallelism = "1 GPU"
-        extra["tiled_1gpu"] = dict(tiled, note="the N > 1 headline's path at one rank: the base of the scaling curve")
+        if full:
+            extra["tiled_1gpu"] = dict(tiled, note="the N > 1 headline's path at one rank: the base of the scaling curve")
         st_frame, s_frame = fl["mean"], fl["elapsed"] / K
+        rays_per_frame, mean_h = fl["rays_total"] / K, fl["mean"]
     else:
         value, ms_per_step, scaling = tiled_value, el_t / K * 1e3, "weak"
         path = tiled["path"]
         parallelism = (f"{world} frames per step, each row-tiled x{world} ({args.band_rows}-row interleaved bands), "
                        "RCCL exchange to per-frame rotating roots")
+        st_frame, s_frame = mean_t, el_t / t_frames * world  # per-GPU wall time per frame of work
+        rays_per_frame, mean_h = (fl["rays_total"] / K, fl["mean"]) if fl else (rays_t / t_frames, mean_t)
+    if dist_mode and full:
         extra["frame_per_gpu"] = {
             "value": round(plain_value, 3), "unit": "Mray/s", "ms_per_step": round(fl["elapsed"] / K * 1e3, 5),
             "workload": f"every rank renders its own whole {args.config} frames, no data-path collective",
@@ -866,13 +922,13 @@ def main():
                        "ms_per_step": round(el_fs / K * 1e3, 5), "frames": K, "frames_per_gather": fpg1,
                        "last_frames_match_trt_render": ok_fs},
             "workload": "every frame row-tiled over all ranks and gathered on rank 0 (the display GPU)"}
-        st_frame, s_frame = mean_t, el_t / t_frames * world  # per-GPU wall time per frame of work
 
-    tiled_c4 = tiled_frame(g, dev, multi, args.tiled_frames, args) if args.tiled_frames > 0 else None
-    multi.close()
+    tiled_c4 = tiled_frame(g, dev, multi, args.tiled_frames, args) if full and args.tiled_frames > 0 else None
+    if multi is not None:
+        multi.close()
 
     extras = {}
-    if args.extra_frames > 0:
+    if full and args.extra_frames > 0:
         for key, name in (("shipped_frame", "ref"), ("readme_frame", "readme")):
             if rank == 0:
                 if not dist_mode:
@@ -884,7 +940,7 @@ def main():
                     extras[key] = extra_frame(dev, name, args.extra_frames, args)
             g.barrier()
 
-    legs = [x for x in args.legs.split(",") if x] if (rank == 0 and not dist_mode) else []
+    legs = [x for x in args.legs.split(",") if x] if (full and rank == 0 and not dist_mode) else []
     for leg in legs:
         key = {"c3": "c3_frame", "c5": "c5_frame", "c2pf": "c2_per_frame_launch", "cabi": "shipped_frame_c_abi"}.get(leg)
         if key is None:
@@ -901,7 +957,8 @@ def main():
         except Exception as e:  # N = 1: report the failure in the line
             extras[key] = {"error": f"{type(e).__name__}: {e}"}
 
-    if rank == 0:
+    rl = None
+    if rank == 0 and full:
         rl = roofline(st_frame, s_frame, envmap, mesh, pixels, fl["kernel_ms_per_frame"] if not dist_mode else None)
         rl["kernel"] = "trace_kernel"
         rl["note"] = ("FP32 flops of one frame's executed work in SURVEY §8d units (counting passes of the camera "
@@ -916,6 +973,7 @@ def main():
             # over the kernel time per frame, or the wall time per frame when the event pass's
             # span is not the shorter one (then the rate is a lower bound)
             attach_traffic(rl, measure_traffic(args, rl.get("kernel_us_per_frame") or rl["us_per_frame"]))
+    if rank == 0:
         result = {
             "metric": METRIC,
             "value": round(value, 3),
@@ -937,24 +995,25 @@ def main():
                 "height": scene.height,
                 "max_depth": scene.max_depth,
                 "spp": scene.spp,
-                "rays_per_frame": round(fl["rays_total"] / K, 1),
-                "shadow_rays_per_frame": round(fl["mean"]["shadow_rays"], 1),
-                "shadow_rays_traced_per_frame": round(fl["mean"]["shadow_rays"] - fl["mean"]["shadow_skipped"], 1),
+                "rays_per_frame": round(rays_per_frame, 1),
+                "shadow_rays_per_frame": round(mean_h["shadow_rays"], 1),
+                "shadow_rays_traced_per_frame": round(mean_h["shadow_rays"] - mean_h["shadow_skipped"], 1),
                 "parallelism": parallelism,
                 "frames_per_step": world,
-                "launches": fl["launches"],
                 "settle_ms": args.settle_ms,
-                "last_frame_matches_trt_render": plain_ok if not dist_mode else tiled_ok,
                 "value_form": "frame per GPU, plain loop" if not dist_mode else
                               "weak: N frames per step, each row-tiled over all ranks, rotating roots",
             },
-            "roofline": rl,
         }
+        if full:  # the event pass, the last-frame check and the roofline are runs of their own
+            result["config"]["launches"] = fl["launches"]
+            result["config"]["last_frame_matches_trt_render"] = plain_ok if not dist_mode else tiled_ok
+            result["roofline"] = rl
         result.update(extra)
         if tiled_c4 is not None:
             result["tiled_frame"] = tiled_c4
         result.update(extras)
-        if not dist_mode and not args.no_cpu:
+        if full and not dist_mode and not args.no_cpu:
             result["cpu_baseline"] = cpu_baseline(scene, scene.params(), rays_of(count_first(dev, scene)),
                                                   args.cpu_seconds)
         print(json.dumps(result), flush=True)

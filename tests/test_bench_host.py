@@ -38,6 +38,29 @@ def test_probe_is_one_timed_size_launch():
     assert b.probe_steps(argparse.Namespace(steps=1000)) == 64
 
 
+def test_plain_run_is_the_default(monkeypatch):
+    """--full is off unless asked for; --dump-outputs takes a directory."""
+    b = _bench()
+    monkeypatch.setattr("sys.argv", ["bench.py", "--gpus", "1", "--steps", "20", "--warmup", "5"])
+    a = b.parse()
+    assert a.full is False and a.dump_outputs is None and (a.steps, a.warmup) == (20, 5)
+    monkeypatch.setattr("sys.argv", ["bench.py", "--full", "--dump-outputs", "d"])
+    a = b.parse()
+    assert a.full is True and a.dump_outputs == Path("d")
+
+
+def test_dump_frame_is_float32_of_the_rgba8_frame(tmp_path):
+    import numpy as np
+    import torch
+
+    b = _bench()
+    frame = torch.arange(2 * 3 * 4, dtype=torch.uint8).reshape(2, 3, 4) * 10
+    b.dump_frame(tmp_path / "out" / "dir", frame)
+    got = np.load(tmp_path / "out" / "dir" / "last_frame.npy")
+    assert got.dtype == np.float32 and got.shape == (2, 3, 4)
+    assert np.array_equal(got, frame.numpy().astype(np.float32))
+
+
 def test_roofline_units():
     """SURVEY 8(d) flop units on a hand-made counter set."""
     b = _bench()

@@ -1,4 +1,4 @@
-"""The N > 1 bench process shape at one rank (bench.py --force-dist): torch.distributed's nccl
+"""The N > 1 bench process shape at one rank (bench.py --full --force-dist): torch.distributed's nccl
 (RCCL) process group and libtrt's own RCCL rank communicator (trt_multi_create_rank, id passed
 through the process group) in ONE process, the tiled weak headline with rotating roots, the
 strong form, the single-root (rank 0) forms and the frame-per-GPU leg — the code the driver's
@@ -22,7 +22,7 @@ REPO = Path(__file__).resolve().parents[1]
 def test_bench_dist_branch_at_one_rank():
     env = dict(os.environ, RANK="0", WORLD_SIZE="1", LOCAL_RANK="0", LOCAL_WORLD_SIZE="1",
                MASTER_ADDR="127.0.0.1", MASTER_PORT=str(random.randint(20000, 40000)))
-    r = subprocess.run([sys.executable, str(REPO / "bench.py"), "--force-dist", "--steps", "8", "--warmup", "2",
+    r = subprocess.run([sys.executable, str(REPO / "bench.py"), "--full", "--force-dist", "--steps", "8", "--warmup", "2",
                         "--no-cpu", "--tiled-frames", "2", "--extra-frames", "0", "--traffic", "off",
                         "--camera-period", "4"], capture_output=True, text=True, timeout=400, env=env, cwd=REPO)
     assert r.returncode == 0, r.stderr[-3000:]

@@ -27,11 +27,11 @@ if [ -z "${SKIP_TESTS:-}" ]; then
     step smoke 400 python -c "import __graft_entry__ as g; g.smoke()"
     step pytest_gpu 900 python -m pytest tests -m gpu -q --timeout 300 ${PYTEST_ARGS:-}
 fi
-step bench 400 python bench.py ${BENCH_ARGS:-}
+step bench 400 python bench.py --full ${BENCH_ARGS:-}
 if [ -n "${PROFILE:-}" ]; then
     export TMPDIR=/tmp
     cd /tmp
     step rocprof_stats 400 rocprofv3 --kernel-trace --stats --output-format csv \
-        -d "$LOG/prof" -o run -- python3 "$ROOT/bench.py" --steps 200 --warmup 10 --no-cpu
+        -d "$LOG/prof" -o run -- python3 "$ROOT/bench.py" --full --steps 200 --warmup 10 --no-cpu
     cd "$ROOT"
 fi

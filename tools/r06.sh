@@ -28,10 +28,10 @@ for stage in "$@"; do
   smoke)
     step smoke 300 python -c "import __graft_entry__ as g; g.smoke()" ;;
   bench) # the driver's command
-    step bench20 600 python bench.py --gpus 1 --steps 20 --warmup 5 ;;
+    step bench20 600 python bench.py --full --gpus 1 --steps 20 --warmup 5 ;;
   prof) # rocprofv3 kernel trace of the bench command, split per (kernel, grid)
     (cd /tmp && export TMPDIR=/tmp && timeout -s KILL 400 rocprofv3 --kernel-trace --stats -d "$OUT/prof" -o run -- \
-      python3 "$ROOT/bench.py" --gpus 1 --steps 20 --warmup 5 --no-cpu --traffic off > "$OUT/prof_bench.log" 2>&1) \
+      python3 "$ROOT/bench.py" --full --gpus 1 --steps 20 --warmup 5 --no-cpu --traffic off > "$OUT/prof_bench.log" 2>&1) \
       || { tail -20 "$OUT/prof_bench.log"; exit 1; }
     db=$(find "$OUT/prof" -name '*.db' | head -1)
     python tools/rocpd_stats.py --split-grid "$db" "$OUT/kernel_stats_by_grid.csv"
