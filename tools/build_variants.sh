@@ -6,7 +6,8 @@ ROOT=$(cd "$(dirname "$0")/.." && pwd)
 SRC=$ROOT/vkcomputeshader_tinyraytracer_amd/csrc
 OUT=$ROOT/variants
 mkdir -p "$OUT" "$ROOT/build/diag"
-FP="-ffp-contract=off -fhip-fp32-correctly-rounded-divide-sqrt -fno-gpu-flush-denormals-to-zero -fno-fast-math -fno-slp-vectorize"
+# the kernel compile flags of the product build: one definition, the Makefile's
+FP=$(make -s -C "$SRC" print-kernel-flags)
 HOST="-O2 -std=c++17 -fPIC -ffp-contract=off -I/opt/rocm/include -D__HIP_PLATFORM_AMD__"
 HDR_NEWEST=$(ls -t "$SRC"/*.h "$ROOT"/include/trt/*.h | head -n 1)
 for f in trt_runtime trt_multi band_plan scene_build obj_load bvh_build image_io jpeg_entropy jpeg_api; do

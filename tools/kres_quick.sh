@@ -5,7 +5,7 @@
 set -e
 ROOT=$(cd "$(dirname "$0")/.." && pwd)
 K="$1"; shift
-FP="-ffp-contract=off -fhip-fp32-correctly-rounded-divide-sqrt -fno-gpu-flush-denormals-to-zero -fno-fast-math -fno-slp-vectorize"
+FP=$(make -s -C "$ROOT/vkcomputeshader_tinyraytracer_amd/csrc" print-kernel-flags) # the product build's flags
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC $FP "-DTRT_KRES_ONLY=$K" "$@" --cuda-device-only -c \
     -o /tmp/kres_quick.co "$ROOT/vkcomputeshader_tinyraytracer_amd/csrc/trt_kernel.hip" -Rpass-analysis=kernel-resource-usage 2>&1 \
     | sed 's/.*remark: //; s/ \[-Rpass-analysis=kernel-resource-usage\]//' \

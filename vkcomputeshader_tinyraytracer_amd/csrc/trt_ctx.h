@@ -46,6 +46,19 @@ struct trt_ctx {
     size_t envp_cap = 0;
     bool envp_ok = false;
     uint32_t nbatch = 0, ntri = 0, nmat = 0, env_w = 0, env_h = 0;
+    // Sky table (KArgs::sky, trt_kernel.hip sky_kernel): width x height RGBA8 words of primary
+    // misses, rebuilt lazily when anything its build reads changes (sky_key; env_gen counts the
+    // envmap uploads).  sky_on: the TRT_SKY_TABLE env knob; sky_ok: d_sky holds sky_key's table
+    // (null: the device had no memory for it, and frames of that key run without one).
+    uint32_t* d_sky = nullptr;
+    size_t sky_cap = 0;
+    bool sky_on = true, sky_ok = false;
+    uint64_t env_gen = 0;
+    struct SkyKey {
+        uint32_t width, height, flags;
+        float dz;
+        uint64_t env_gen;
+    } sky_key{};
 
     void* d_out8 = nullptr;
     size_t cap8 = 0;

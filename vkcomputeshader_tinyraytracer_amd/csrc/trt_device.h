@@ -254,6 +254,9 @@ struct KArgs {
     size_t ev_fstride, shq_fstride;
     uint32_t spp_lanes;               // spp > 1: one lane per sample (trace_samples), spp waves per tile
     FrameRec fr[kMaxLaunchFrames];    // camera + output of each frame of the launch
+    // Sky table (sky_kernel): the packed RGBA8 word of a primary miss of frame pixel y * width + x,
+    // or null (the per-ray background path).  Set for plain spp-1 frames without rays_in / out32.
+    const uint32_t* __restrict__ sky;
 };
 static_assert(sizeof(KArgs) <= 4096, "KArgs fits the 4 KB kernel-argument limit");
 

@@ -3,15 +3,18 @@
 // MI355X.
 //
 // Execution model
-//   * One lane per pixel (per sample when spp > 1); a wave64 owns an 8x8 pixel tile and a
-//     256-thread workgroup a 16x16 tile, so a wave's rays stay coherent and the batch /
-//     triangle walks below are shared by all 64 lanes.
+//   * One lane per pixel (per sample when spp > 1); a workgroup is one wave64 and owns an 8x8
+//     pixel tile (of one frame, or of two consecutive frames of a multi-frame launch), so a
+//     wave's rays stay coherent and the batch / triangle walks below are shared by all 64
+//     lanes.  The hardware dispatcher deals the tiles to the freed wave slots.
 //   * The UBO (spheres, lights, camera; binding 0) rides in the kernarg segment (SGPRs).
-//   * scene_intersect / shadow_intersect walk the AABB batches in index order exactly as
-//     shader.comp:338-361 / 379-396 do, but wave-uniformly: a batch record is one scalar
-//     load shared by the wave, `__ballot` over the lanes' slab tests skips a batch no lane
-//     hits, and the hit batch's triangles are streamed as wave-uniform scalar loads
-//     (v0, e1, e2 pre-subtracted on the host with the shader's own subtraction).
+//   * scene_intersect / shadow_intersect test the floor and the spheres per lane; triangles
+//     go through a per-lane walk of a 4-wide quantized BVH (GEOM 2 / 3), or, on request, the
+//     reference-order batch walk (GEOM 1: shader.comp:338-361 / 379-396 wave-uniformly, batch
+//     records and triangles as scalar loads shared by the wave).
+//   * A triangle-free tile whose primary rays all miss stores its pixels from the sky table
+//     (sky_kernel: the word a primary miss of each pixel packs to, built once per resolution
+//     and envmap) and skips the background, gamma and pack of that frame.
 //   * The reference's 40-entry PathSegment stack with 32-entry volume stacks (~80 KB of
 //     private memory per invocation) becomes "current segment + deferred
 //     refraction children": the volume stack is provably inert and the
@@ -1589,21 +1592,24 @@ __device__ __forceinline__ MatVals load_mat(const KArgs& A, int kind, int idx, f
 // HYB: the deferred refraction children live in CAP LDS entries plus a private tail.  (The
 // shading here is written out rather than through resolve_hit / light_term / make_children:
 // the factored form compiles the C2 and C4 kernels with more live registers — C2 spilled.)
-template <int CAP, bool COUNT, int GEOM, bool SPLIT, bool HYB = SPLIT>
+// ROOT: the caller has already intersected `cur` (trace_tile's sky test) and passes its hit in
+// `root`, so the segment is not tested twice.
+template <int CAP, bool COUNT, int GEOM, bool SPLIT, bool HYB = SPLIT, bool ROOT = false>
 __device__ __forceinline__ f3 cast_seg(const KArgs& A, Seg cur, Cnt& cnt, float* lds, float4* slab,
-                                       uint32_t pixel, bool& spilled) {
+                                       uint32_t pixel, bool& spilled, const Hit* root = nullptr) {
     const int D = (int)A.max_depth;
     f3 color = mk(0.0f, 0.0f, 0.0f);
     using Stk = typename StackOf<CAP, HYB, GEOM>::type;
     typename Stk::Mem stk_mem;
     Stk stk(lds, stk_mem);
+    Hit h;
+    if constexpr (ROOT) h = *root;
     for (;;) {
         if (COUNT && cur.depth > 0) ++cnt.sec;
 #ifdef TRT_DIAG_PIXEL_WORK
         ++cnt.wseg;
 #endif
-        Hit h;
-        scene_intersect<COUNT, GEOM>(A, cur.o, cur.d, h, cnt, slab);
+        if constexpr (!ROOT) scene_intersect<COUNT, GEOM>(A, cur.o, cur.d, h, cnt, slab);
         bool have_next = false;
         Seg next;
         if (h.kind == HIT_NONE) {
@@ -1829,6 +1835,9 @@ __device__ __forceinline__ f3 cast_seg(const KArgs& A, Seg cur, Cnt& cnt, float*
         } else {
             break;
         }
+        // ROOT: the loop is rotated (the next segment's test at its end), so the root hit is
+        // the loop's first `h` and nothing of it stays live across the iterations
+        if constexpr (ROOT) scene_intersect<COUNT, GEOM>(A, cur.o, cur.d, h, cnt, slab);
     }
     return color;
 }
@@ -2153,14 +2162,42 @@ __device__ __forceinline__ unsigned long long wave_sum(unsigned long long x) {
     return x;
 }
 
-// Gamma (shader.comp:598) and the dual store (rayOut binding 2, storage image binding 3) of
-// output pixel o; `c` is the clamped colour.
-__device__ __forceinline__ void store_pixel(const KArgs& A, const FrameRec& F, size_t o, f3 c) {
-    if (F.in_place) { // compact row k -> its frame row (band_row)
+// Where output pixel o of the compact rows is written: a band launch in place writes compact row
+// k at its frame row (band_row).
+__device__ __forceinline__ size_t out_index(const KArgs& A, const FrameRec& F, size_t o) {
+    if (F.in_place) {
         const uint32_t k = (uint32_t)(o / A.width), x = (uint32_t)(o % A.width);
         o = (size_t)band_row(A, k) * A.width + x;
     }
-    const float gx = pow_pos(c.x, TRT_GAMMA), gy = pow_pos(c.y, TRT_GAMMA), gz = pow_pos(c.z, TRT_GAMMA);
+    return o;
+}
+
+// Gamma, shader.comp:598; `c` is the clamped colour.
+__device__ __forceinline__ f3 gamma3(f3 c) {
+    return mk(pow_pos(c.x, TRT_GAMMA), pow_pos(c.y, TRT_GAMMA), pow_pos(c.z, TRT_GAMMA));
+}
+
+// The rgba8 storage image's word (shader.comp:61, 600) of a gamma-encoded colour.  The one
+// pack of store_pixel and of the sky table's build (sky_kernel), so both give the same bits.
+__device__ __forceinline__ uint32_t pack_rgba8(const KArgs& A, f3 g) {
+    float ex = g.x, ey = g.y, ez = g.z;
+    if (A.flags & TRT_FLAG_SRGB_OUT) { // as displayed through the sRGB swapchain
+        ex = srgb_encode(g.x);
+        ey = srgb_encode(g.y);
+        ez = srgb_encode(g.z);
+    }
+    uint32_t r = (uint32_t)floorf(ex * 255.0f + 0.5f);
+    uint32_t gg = (uint32_t)floorf(ey * 255.0f + 0.5f);
+    uint32_t b = (uint32_t)floorf(ez * 255.0f + 0.5f);
+    return r | (gg << 8) | (b << 16) | (255u << 24);
+}
+
+// Gamma and the dual store (rayOut binding 2, storage image binding 3) of output pixel o; `c`
+// is the clamped colour.
+__device__ __forceinline__ void store_pixel(const KArgs& A, const FrameRec& F, size_t o, f3 c) {
+    o = out_index(A, F, o);
+    const f3 g = gamma3(c);
+    const float gx = g.x, gy = g.y, gz = g.z;
 #ifdef TRT_DIAG_WAVE_CLOCK
     if (false) // out32 carries the workgroup clock records
 #else
@@ -2169,18 +2206,7 @@ __device__ __forceinline__ void store_pixel(const KArgs& A, const FrameRec& F, s
     {
         reinterpret_cast<float4*>(A.out32)[o] = make_float4(gx, gy, gz, 1.0f);
     }
-    if (F.out8) { // rgba8 storage image, shader.comp:61, 600
-        float ex = gx, ey = gy, ez = gz;
-        if (A.flags & TRT_FLAG_SRGB_OUT) { // as displayed through the sRGB swapchain
-            ex = srgb_encode(gx);
-            ey = srgb_encode(gy);
-            ez = srgb_encode(gz);
-        }
-        uint32_t r = (uint32_t)floorf(ex * 255.0f + 0.5f);
-        uint32_t g = (uint32_t)floorf(ey * 255.0f + 0.5f);
-        uint32_t b = (uint32_t)floorf(ez * 255.0f + 0.5f);
-        F.out8[o] = r | (g << 8) | (b << 16) | (255u << 24);
-    }
+    if (F.out8) F.out8[o] = pack_rgba8(A, g);
 }
 
 // One 8x8 pixel tile of compact output rows: the wave's 64 lanes, one pixel each.  SPLIT
@@ -2191,7 +2217,7 @@ __device__ __forceinline__ void store_pixel(const KArgs& A, const FrameRec& F, s
 // its other lanes take work from the wave's segment pool as the trees grow, so a glass tile's
 // segments are spread over more waves (a shorter frame latency) at the price of idle lanes in
 // cheap tiles.
-template <int CAP, bool COUNT, int GEOM, bool SPLIT, bool DEFER = false, bool HYB = SPLIT>
+template <int CAP, bool COUNT, int GEOM, bool SPLIT, bool DEFER = false, bool HYB = SPLIT, bool SKY = false>
 __device__ __forceinline__ void trace_tile(const KArgs& A, const FrameRec& F, uint32_t tile, Cnt& cnt, float* lds,
                                            float4* slab, uint32_t sub = 0, uint32_t frame = 0) {
     const uint32_t lane = lane_id();
@@ -2243,6 +2269,30 @@ __device__ __forceinline__ void trace_tile(const KArgs& A, const FrameRec& F, ui
         }
         if (!spilled) store_pixel(A, F, o, mk(clamp01(c.x), clamp01(c.y), clamp01(c.z)));
         return;
+    }
+    if constexpr (SKY) {
+        // Sky table (sky_trace_kernel: triangle-free spp-1 frames without rays_in / out32, A.sky
+        // set): the primary rays are intersected here, and a wave whose rays all miss stores the
+        // words a primary miss of its pixels packs to (the camera only translates, so they are
+        // the same in every frame) and is done.  The load is issued before the tests and its
+        // word is dead after the ballot; any other wave hands its root hits to cast_seg (ROOT),
+        // and the missing lanes of a mixed tile take the per-ray background as before.
+        static_assert(!SKY || (GEOM == 0 && !COUNT && !SPLIT && !DEFER), "the sky table serves plain GEOM 0 frames");
+        {
+            const f3 d = primary_dir(A, x, y, 0);
+            const uint32_t word = A.sky[(size_t)y * A.width + x];
+            Hit h;
+            scene_intersect<false, 0>(A, orig, d, h, cnt, slab);
+            if (__ballot(h.kind != HIT_NONE) == 0ull) {
+                if (F.out8) F.out8[out_index(A, F, o)] = word;
+                return;
+            }
+            bool unused = false;
+            const f3 c = cast_seg<CAP, false, 0, false, false, true>(A, Seg{orig, d, 1.0f, 0}, cnt, lds, slab, 0u,
+                                                                     unused, &h);
+            store_pixel(A, F, o, mk(clamp01(c.x), clamp01(c.y), clamp01(c.z))); // cast_ray's clamp
+            return;
+        }
     }
     const uint32_t spp = A.spp ? A.spp : 1u;
     f3 acc = mk(0.0f, 0.0f, 0.0f);
@@ -2433,8 +2483,8 @@ constexpr int trace_waves() {
     return (DEFER && GEOM == 3) ? TRT_DEFER_WAVES : waves_per_simd<GEOM, ((SPLIT || DEFER) ? 99 : CAP)>();
 }
 
-template <int CAP, bool COUNT, int GEOM, bool SPLIT, bool DEFER = false, bool HYB = SPLIT>
-__global__ __launch_bounds__(64, (trace_waves<GEOM, CAP, SPLIT, DEFER>())) void trace_kernel(KArgs A) {
+template <int CAP, bool COUNT, int GEOM, bool SPLIT, bool DEFER, bool HYB, bool SKY>
+__device__ __forceinline__ void trace_body(const KArgs& A) {
     __shared__ float lds[DEFER ? defer_pool_floats() : lds_stack_floats<CAP, GEOM, HYB>()];
     // GEOM 1: one batch slab, 64 x (v0, e1, e2); GEOM 2: the BVH traversal stacks
     __shared__ float4 slab[slab_float4s<GEOM>()];
@@ -2468,8 +2518,8 @@ __global__ __launch_bounds__(64, (trace_waves<GEOM, CAP, SPLIT, DEFER>())) void 
             uint32_t pr;
             tile = inter_tile(A, vb, pr, (A.nframes + 1u) / 2u);
             f = 2u * pr;
-            trace_tile<CAP, COUNT, GEOM, SPLIT, DEFER, HYB>(A, A.fr[f], tile, cnt, lds, slab);
-            if (f + 1u < A.nframes) trace_tile<CAP, COUNT, GEOM, SPLIT, DEFER, HYB>(A, A.fr[f + 1u], tile, cnt, lds, slab);
+            trace_tile<CAP, COUNT, GEOM, SPLIT, DEFER, HYB, SKY>(A, A.fr[f], tile, cnt, lds, slab);
+            if (f + 1u < A.nframes) trace_tile<CAP, COUNT, GEOM, SPLIT, DEFER, HYB, SKY>(A, A.fr[f + 1u], tile, cnt, lds, slab);
             if (COUNT) flush_counts(A, cnt);
             return;
         } else if (A.xcd_inter) {
@@ -2521,7 +2571,7 @@ __global__ __launch_bounds__(64, (trace_waves<GEOM, CAP, SPLIT, DEFER>())) void 
     } else {
         tile = xcd_tile(A, t);
     }
-    trace_tile<CAP, COUNT, GEOM, SPLIT, DEFER, HYB>(A, A.fr[f], tile, cnt, lds, slab);
+    trace_tile<CAP, COUNT, GEOM, SPLIT, DEFER, HYB, SKY>(A, A.fr[f], tile, cnt, lds, slab);
 #ifdef TRT_DIAG_WAVE_CLOCK
     __syncthreads();
     // single-frame launches write the records to out32; multi-frame launches to the diagnostic
@@ -2539,6 +2589,18 @@ __global__ __launch_bounds__(64, (trace_waves<GEOM, CAP, SPLIT, DEFER>())) void 
     }
 #endif
     if (COUNT) flush_counts(A, cnt);
+}
+
+template <int CAP, bool COUNT, int GEOM, bool SPLIT, bool DEFER = false, bool HYB = SPLIT>
+__global__ __launch_bounds__(64, (trace_waves<GEOM, CAP, SPLIT, DEFER>())) void trace_kernel(KArgs A) {
+    trace_body<CAP, COUNT, GEOM, SPLIT, DEFER, HYB, false>(A);
+}
+
+// The plain triangle-free frame with the sky table (A.sky set, spp 1, no rays_in / out32): a
+// kernel of its own, so that frames without a table run trace_kernel exactly as before.
+template <int CAP>
+__global__ __launch_bounds__(64, (trace_waves<0, CAP, false, false>())) void sky_trace_kernel(KArgs A) {
+    trace_body<CAP, false, 0, false, false, false, true>(A);
 }
 
 // One round of a split frame: persistent waves take 64 tasks at a time (static schedule) from
@@ -2917,9 +2979,12 @@ hipError_t launch_trace(const KArgs& A, hipStream_t stream, bool count) {
                                  ? (A.nframes + 1u) / 2u
                                  : std::max(A.nframes, 1u);
     const dim3 fgrid(A.ntiles * fblocks);
+    // the sky table's kernel: what the host's conditions (attach_sky) promise, checked again
+    const bool sky = A.sky && geom == 0 && !count && A.spp <= 1 && !A.rays_in && !A.out32;
 #define TRT_LAUNCH_G(CAP, G)                                                                             \
     do {                                                                                                 \
         if (count) hipLaunchKernelGGL((trace_kernel<CAP, true, G, false>), fgrid, block, 0, stream, A);  \
+        else if (G == 0 && sky) hipLaunchKernelGGL((sky_trace_kernel<CAP>), fgrid, block, 0, stream, A); \
         else hipLaunchKernelGGL((trace_kernel<CAP, false, G, false>), fgrid, block, 0, stream, A);       \
     } while (0)
 #define TRT_LAUNCH(CAP)                          \
@@ -2960,6 +3025,36 @@ __global__ __launch_bounds__(256) void envp_kernel(const uint32_t* __restrict__ 
 hipError_t launch_envp(const uint32_t* env, uint2* out, uint32_t W, uint32_t H, hipStream_t stream) {
     if (!W || !H) return hipSuccess;
     hipLaunchKernelGGL(envp_kernel, dim3((W + 3u + 255u) / 256u, H + 2u), dim3(256), 0, stream, env, out, W, H);
+    return hipGetLastError();
+}
+
+} // namespace trt
+
+// ---- sky table (KArgs::sky) ----------------------------------------------------------------
+//
+// Entry y * width + x is the RGBA8 word store_pixel writes for a primary ray of frame pixel
+// (x, y) that misses the scene: the ray's direction depends only on the pixel (the camera only
+// translates, main.cpp:391-403; the reference itself builds its directions once, :1496-1506), and
+// a miss's colour only on the direction and the envmap.  Built with the frame's own functions
+// (primary_dir, background, cast_seg's accumulation, cast_ray's clamp, gamma3, pack_rgba8), so
+// the words are the frame's bit for bit.  A: the frame's arguments with spp 1 and no rays_in.
+namespace trt {
+
+__global__ __launch_bounds__(256) void sky_kernel(KArgs A, uint32_t* __restrict__ out) {
+    const uint32_t x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y;
+    if (x >= A.width || y >= A.height) return;
+    const f3 d = primary_dir(A, x, y, 0);
+    const f3 bg = background(A, d);
+    const f3 c = add(mk(0.0f, 0.0f, 0.0f), muls(bg, 1.0f));
+    out[(size_t)y * A.width + x] = pack_rgba8(A, gamma3(mk(clamp01(c.x), clamp01(c.y), clamp01(c.z))));
+}
+
+hipError_t launch_sky(const KArgs& A0, uint32_t* out, hipStream_t stream) {
+    if (!A0.width || !A0.height) return hipSuccess;
+    KArgs A = A0;
+    A.spp = 1;
+    A.rays_in = nullptr;
+    hipLaunchKernelGGL(sky_kernel, dim3((A.width + 255u) / 256u, A.height), dim3(256), 0, stream, A, out);
     return hipGetLastError();
 }
 

@@ -37,6 +37,7 @@ hipError_t touch_stream(hipStream_t s, void* scratch) {
 }
 hipError_t launch_trace(const KArgs& A, hipStream_t stream, bool count);
 hipError_t launch_envp(const uint32_t* env, uint2* out, uint32_t W, uint32_t H, hipStream_t stream);
+hipError_t launch_sky(const KArgs& A, uint32_t* out, hipStream_t stream);
 hipError_t launch_shadow_batch(const KArgs& A, const float4* rays, uint32_t n, uint32_t* occ, hipStream_t stream);
 uint32_t collapse_bvh4(const std::vector<BvhNode>& b2, std::vector<Bvh4Node>& b4);
 uint32_t bvh_depth(const std::vector<BvhNode>& b2);
@@ -103,6 +104,7 @@ void free_scene(trt_ctx* c) {
     c->d_mats = nullptr;
     c->d_env = nullptr;
     c->envp_ok = false;
+    ++c->env_gen;
     c->nbatch = c->ntri = c->nmat = c->env_w = c->env_h = 0;
     std::memset(c->scene_bytes, 0, sizeof(c->scene_bytes));
     c->have_scene = false;
@@ -237,6 +239,7 @@ int trt_create(trt_ctx** out, int hip_device) {
     if (const char* e = std::getenv("TRT_XCD_SKEW")) c->xcd_skew = (uint32_t)std::min(7, std::max(0, std::atoi(e)));
     if (const char* e = std::getenv("TRT_XCD_INTER")) c->xcd_inter = (uint32_t)std::min(2, std::max(0, std::atoi(e)));
     if (const char* e = std::getenv("TRT_FRAME_GROUP")) c->frame_group = std::min(2, std::max(1, std::atoi(e)));
+    if (const char* e = std::getenv("TRT_SKY_TABLE")) c->sky_on = std::atoi(e) != 0;
     *out = c;
     return TRT_OK;
 }
@@ -251,6 +254,7 @@ int trt_destroy(trt_ctx* c) {
     (void)hipDeviceSynchronize();
     free_scene(c);
     (void)hipFree(c->d_envp);
+    (void)hipFree(c->d_sky);
     (void)hipFree(c->d_out8);
     (void)hipFree(c->d_out32);
     (void)hipFree(c->d_rays);
@@ -572,6 +576,57 @@ int ensure_envp(trt_ctx* c, const trt_params* p, hipStream_t stream) {
     // ordered after `stream` (trt_multi's two batch slots fork before the first batch builds)
     HIP_TRY(c, hipStreamSynchronize(stream));
     c->envp_ok = true;
+    return TRT_OK;
+}
+
+// The sky table of a frame's arguments (KArgs::sky), or null when the frame does not use one.
+// The table serves triangle-free plain frames at spp 1 that neither replay rays (rays_in) nor
+// write rayOut (out32) nor count; A carries all of that (fill_args, then the caller's rays_in /
+// out32).  It is rebuilt on `stream` when anything sky_kernel reads has changed: the image
+// size, dz, the flags that shape a primary ray or the pack, or the envmap.  Frames of earlier
+// calls may still read the old table on other streams (frames in flight, trt_render on
+// alternating streams), so a rebuild first drains the device; like ensure_envp it then waits
+// for the build, since later frames may run on streams not ordered after `stream`.  Both happen
+// once per change, never in a frame loop.  The drain is of the whole device, not only of this
+// context's slot streams: trt_render may have been given any stream of the caller's
+// (trt_set_stream), which the context does not keep.  A context holds ONE table: a caller that
+// alternates two keys on it (two resolutions, sRGB on and off) rebuilds on every switch, a
+// drain and one small kernel each time; such a caller uses one context per key or switches the
+// table off (TRT_SKY_TABLE=0).  Without device memory for the table the frames run without it.
+int attach_sky(trt_ctx* c, KArgs& A, bool count, hipStream_t stream) {
+    A.sky = nullptr;
+    if (!c->sky_on || c->nbatch != 0 || A.spp > 1 || A.rays_in || A.out32 || count) return TRT_OK;
+    if ((A.flags & TRT_FLAG_ENVMAP) && !c->d_env) return TRT_OK;
+    const uint32_t kflags = A.flags & (TRT_FLAG_ROW_QUIRK | TRT_FLAG_SRGB_OUT | TRT_FLAG_ENVMAP);
+    const trt_ctx::SkyKey key{A.width, A.height, kflags, A.dz, (A.flags & TRT_FLAG_ENVMAP) ? c->env_gen : 0u};
+    const trt_ctx::SkyKey& k = c->sky_key;
+    const bool same = c->sky_ok && k.width == key.width && k.height == key.height && k.flags == key.flags &&
+                      std::memcmp(&k.dz, &key.dz, sizeof(float)) == 0 && k.env_gen == key.env_gen;
+    if (!same) {
+        c->sky_ok = false;
+        HIP_TRY(c, hipDeviceSynchronize());
+        const size_t bytes = (size_t)A.width * A.height * sizeof(uint32_t);
+        if (bytes > c->sky_cap || !c->d_sky) {
+            (void)hipFree(c->d_sky);
+            c->d_sky = nullptr;
+            c->sky_cap = 0;
+            const hipError_t e = hipMalloc((void**)&c->d_sky, bytes);
+            if (e == hipErrorOutOfMemory) {
+                (void)hipGetLastError(); // not the next launch's error
+                c->d_sky = nullptr;
+                c->sky_key = key; // frames of this key run without a table: no retry per call
+                c->sky_ok = true;
+                return TRT_OK;
+            }
+            HIP_TRY(c, e);
+            c->sky_cap = bytes;
+        }
+        HIP_TRY(c, trt::launch_sky(A, c->d_sky, stream));
+        HIP_TRY(c, hipStreamSynchronize(stream));
+        c->sky_key = key;
+        c->sky_ok = true;
+    }
+    A.sky = c->d_sky;
     return TRT_OK;
 }
 
@@ -981,6 +1036,7 @@ int render_frame_list(trt_ctx* c, const trt_params* p, const FrameOut* frames, u
     KArgs A;
     fill_args(c, p, A);
     A.rays_in = reinterpret_cast<const float*>(p->rays_in);
+    if (A.rows != 0 && nframes != 0 && (rc = attach_sky(c, A, false, c->stream)) != TRT_OK) return rc;
     auto ubo_of = [&](uint32_t i) -> const trt_ubo& { return frames[i].ubo ? *frames[i].ubo : c->ubo; };
     if (A.rows == 0 || nframes == 0) {
         if (nframes) c->ubo = ubo_of(nframes - 1);
@@ -1176,6 +1232,7 @@ int trt_render(trt_ctx* c, const trt_params* p, uint8_t* out8, float* out32, trt
             A.out32 = reinterpret_cast<float*>(c->d_out32);
         }
     }
+    if (npx > 0 && (rc = attach_sky(c, A, count, c->stream)) != TRT_OK) return rc;
     const uint32_t slot = render_slot(c, c->stream);
     c->cur_in_flight = 1u; // one frame: its latency is the rate
     if ((rc = prepare_split(c, p, A, slot, c->stream)) != TRT_OK) return rc;
@@ -1278,6 +1335,7 @@ extern "C" int trt_upload_envmap_jpeg(trt_ctx* c, const uint8_t* data, size_t le
     (void)hipFree(c->d_env);
     c->d_env = d;
     c->envp_ok = false;
+    ++c->env_gen;
     c->env_w = (uint32_t)im->width;
     c->env_h = (uint32_t)im->height;
     c->scene_bytes[trt::kSceneEnv] = (size_t)im->width * im->height * 4;
