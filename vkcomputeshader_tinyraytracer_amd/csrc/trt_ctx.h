@@ -53,6 +53,11 @@ struct trt_ctx {
     uint32_t* d_sky = nullptr;
     size_t sky_cap = 0;
     bool sky_on = true, sky_ok = false;
+    // Sky spans (KArgs::span, sky_spans.h) of every launch that has a sky table.  span_on: the
+    // TRT_SKY_SPANS env knob; span_frames: frames per span table (TRT_SKY_SPAN_FRAMES; 0 = one
+    // table per launch)
+    bool span_on = true;
+    uint32_t span_frames = 16;
     uint64_t env_gen = 0;
     struct SkyKey {
         uint32_t width, height, flags;

@@ -13,6 +13,8 @@
 
 #include <hip/hip_runtime.h>
 
+#include "sky_spans.h"
+
 namespace trt {
 
 // One AABB batch (Model, shader.comp:29-38): bbox + triangle range + smooth flag.
@@ -257,6 +259,12 @@ struct KArgs {
     // Sky table (sky_kernel): the packed RGBA8 word of a primary miss of frame pixel y * width + x,
     // or null (the per-ray background path).  Set for plain spp-1 frames without rays_in / out32.
     const uint32_t* __restrict__ sky;
+    // Sky spans (sky_spans.h; sky_trace_kernel only): span_tables tables of span_ntr words, one per
+    // tile row of the launch, table f >> span_shift for frame f: the tile columns [c0, c1) = [word &
+    // 0xffff, word >> 16) outside which every tile is all sky in every frame of the table.
+    // span_tables 0: none (always so when sky is null).
+    uint32_t span_tables, span_shift, span_ntr;
+    uint32_t span[kSpanWords];
 };
 static_assert(sizeof(KArgs) <= 4096, "KArgs fits the 4 KB kernel-argument limit");
 

@@ -14,7 +14,9 @@
 //     records and triangles as scalar loads shared by the wave).
 //   * A triangle-free tile whose primary rays all miss stores its pixels from the sky table
 //     (sky_kernel: the word a primary miss of each pixel packs to, built once per resolution
-//     and envmap) and skips the background, gamma and pack of that frame.
+//     and envmap) and skips the background, gamma and pack of that frame.  Where the host
+//     could prove from the launch's UBOs that no primary ray of a tile hits anything (sky
+//     spans, sky_spans.h), the tile stores those words without tracing its primary rays.
 //   * The reference's 40-entry PathSegment stack with 32-entry volume stacks (~80 KB of
 //     private memory per invocation) becomes "current segment + deferred
 //     refraction children": the volume stack is provably inert and the
@@ -2209,6 +2211,30 @@ __device__ __forceinline__ void store_pixel(const KArgs& A, const FrameRec& F, s
     if (F.out8) F.out8[o] = pack_rgba8(A, g);
 }
 
+// Sky spans (KArgs::span, sky_spans.h): the span word of `tile` in frame f of the launch.  Both
+// are wave-uniform, so this is scalar work and one scalar load from the kernel arguments.
+__device__ __forceinline__ uint32_t span_word(const KArgs& A, uint32_t tile, uint32_t f) {
+    if (A.span_tables == 0u || tile >= A.ntiles) return kSpanFull;
+    return A.span[(f >> A.span_shift) * A.span_ntr + tile / A.ntx];
+}
+__device__ __forceinline__ bool span_outside(const KArgs& A, uint32_t tile, uint32_t span) {
+    const uint32_t col = tile % A.ntx;
+    return col < (span & 0xffffu) || col >= (span >> 16);
+}
+
+// A tile outside its row's span: no primary ray of F0 (or of F1, the second frame of a pair, if
+// any) hits anything, so its pixels are their sky-table words — one load, a store per frame, no
+// primary ray generated or intersected.
+__device__ __forceinline__ void sky_tile_store(const KArgs& A, uint32_t tile, const FrameRec& F0, const FrameRec* F1) {
+    const uint32_t lane = lane_id();
+    const uint32_t x = (tile % A.ntx) * 8u + (lane & 7u), k = (tile / A.ntx) * 8u + (lane >> 3);
+    if (x >= A.width || k >= A.rows) return;
+    const uint32_t word = A.sky[(size_t)band_row(A, k) * A.width + x];
+    const size_t o = (size_t)k * A.width + x;
+    if (F0.out8) F0.out8[out_index(A, F0, o)] = word;
+    if (F1 && F1->out8) F1->out8[out_index(A, *F1, o)] = word;
+}
+
 // One 8x8 pixel tile of compact output rows: the wave's 64 lanes, one pixel each.  SPLIT
 // (spp == 1 only): a pixel whose tree handed subtrees to the task queue parks its partial
 // colour in A.acc and is finished by finalize_spilled.
@@ -2483,8 +2509,9 @@ constexpr int trace_waves() {
     return (DEFER && GEOM == 3) ? TRT_DEFER_WAVES : waves_per_simd<GEOM, ((SPLIT || DEFER) ? 99 : CAP)>();
 }
 
-template <int CAP, bool COUNT, int GEOM, bool SPLIT, bool DEFER, bool HYB, bool SKY>
+template <int CAP, bool COUNT, int GEOM, bool SPLIT, bool DEFER, bool HYB, bool SKY, bool SPANS = false>
 __device__ __forceinline__ void trace_body(const KArgs& A) {
+    static_assert(!SPANS || SKY, "the sky spans cull into the sky table");
     __shared__ float lds[DEFER ? defer_pool_floats() : lds_stack_floats<CAP, GEOM, HYB>()];
     // GEOM 1: one batch slab, 64 x (v0, e1, e2); GEOM 2: the BVH traversal stacks
     __shared__ float4 slab[slab_float4s<GEOM>()];
@@ -2518,6 +2545,14 @@ __device__ __forceinline__ void trace_body(const KArgs& A) {
             uint32_t pr;
             tile = inter_tile(A, vb, pr, (A.nframes + 1u) / 2u);
             f = 2u * pr;
+#ifndef TRT_DIAG_TRIVIAL
+            if constexpr (SPANS) { // a pair never straddles two span tables (span_shift >= 1)
+                if (span_outside(A, tile, span_word(A, tile, f))) {
+                    sky_tile_store(A, tile, A.fr[f], f + 1u < A.nframes ? &A.fr[f + 1u] : nullptr);
+                    return;
+                }
+            }
+#endif
             trace_tile<CAP, COUNT, GEOM, SPLIT, DEFER, HYB, SKY>(A, A.fr[f], tile, cnt, lds, slab);
             if (f + 1u < A.nframes) trace_tile<CAP, COUNT, GEOM, SPLIT, DEFER, HYB, SKY>(A, A.fr[f + 1u], tile, cnt, lds, slab);
             if (COUNT) flush_counts(A, cnt);
@@ -2571,6 +2606,14 @@ __device__ __forceinline__ void trace_body(const KArgs& A) {
     } else {
         tile = xcd_tile(A, t);
     }
+#if !defined(TRT_DIAG_TRIVIAL) && !defined(TRT_DIAG_WAVE_CLOCK)
+    if constexpr (SPANS) {
+        if (span_outside(A, tile, span_word(A, tile, f))) {
+            sky_tile_store(A, tile, A.fr[f], nullptr);
+            return;
+        }
+    }
+#endif
     trace_tile<CAP, COUNT, GEOM, SPLIT, DEFER, HYB, SKY>(A, A.fr[f], tile, cnt, lds, slab);
 #ifdef TRT_DIAG_WAVE_CLOCK
     __syncthreads();
@@ -2598,9 +2641,16 @@ __global__ __launch_bounds__(64, (trace_waves<GEOM, CAP, SPLIT, DEFER>())) void 
 
 // The plain triangle-free frame with the sky table (A.sky set, spp 1, no rays_in / out32): a
 // kernel of its own, so that frames without a table run trace_kernel exactly as before.
+// With the sky spans (A.span_tables != 0) a tile outside its row's span is stored without its
+// primary rays; a launch without spans runs the kernel without the span test, exactly the code it
+// ran before there were spans.
 template <int CAP>
 __global__ __launch_bounds__(64, (trace_waves<0, CAP, false, false>())) void sky_trace_kernel(KArgs A) {
-    trace_body<CAP, false, 0, false, false, false, true>(A);
+    trace_body<CAP, false, 0, false, false, false, true, true>(A);
+}
+template <int CAP>
+__global__ __launch_bounds__(64, (trace_waves<0, CAP, false, false>())) void sky_trace_kernel_nospan(KArgs A) {
+    trace_body<CAP, false, 0, false, false, false, true, false>(A);
 }
 
 // One round of a split frame: persistent waves take 64 tasks at a time (static schedule) from
@@ -2984,7 +3034,8 @@ hipError_t launch_trace(const KArgs& A, hipStream_t stream, bool count) {
 #define TRT_LAUNCH_G(CAP, G)                                                                             \
     do {                                                                                                 \
         if (count) hipLaunchKernelGGL((trace_kernel<CAP, true, G, false>), fgrid, block, 0, stream, A);  \
-        else if (G == 0 && sky) hipLaunchKernelGGL((sky_trace_kernel<CAP>), fgrid, block, 0, stream, A); \
+        else if (G == 0 && sky && A.span_tables) hipLaunchKernelGGL((sky_trace_kernel<CAP>), fgrid, block, 0, stream, A); \
+        else if (G == 0 && sky) hipLaunchKernelGGL((sky_trace_kernel_nospan<CAP>), fgrid, block, 0, stream, A); \
         else hipLaunchKernelGGL((trace_kernel<CAP, false, G, false>), fgrid, block, 0, stream, A);       \
     } while (0)
 #define TRT_LAUNCH(CAP)                          \

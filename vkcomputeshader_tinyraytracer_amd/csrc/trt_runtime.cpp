@@ -240,6 +240,8 @@ int trt_create(trt_ctx** out, int hip_device) {
     if (const char* e = std::getenv("TRT_XCD_INTER")) c->xcd_inter = (uint32_t)std::min(2, std::max(0, std::atoi(e)));
     if (const char* e = std::getenv("TRT_FRAME_GROUP")) c->frame_group = std::min(2, std::max(1, std::atoi(e)));
     if (const char* e = std::getenv("TRT_SKY_TABLE")) c->sky_on = std::atoi(e) != 0;
+    if (const char* e = std::getenv("TRT_SKY_SPANS")) c->span_on = std::atoi(e) != 0;
+    if (const char* e = std::getenv("TRT_SKY_SPAN_FRAMES")) c->span_frames = (uint32_t)std::min(64, std::max(0, std::atoi(e)));
     *out = c;
     return TRT_OK;
 }
@@ -628,6 +630,37 @@ int attach_sky(trt_ctx* c, KArgs& A, bool count, hipStream_t stream) {
     }
     A.sky = c->d_sky;
     return TRT_OK;
+}
+
+// The sky spans of a launch (KArgs::span), from what the launch's arguments already hold: the
+// frames' cameras (fill_frame), the UBO's spheres (fill_ubo_args) and the sky table (attach_sky).
+// Unset wherever there is no table, and under TRT_SKY_SPANS=0.
+void fill_spans(const trt_ctx* c, KArgs& A) {
+    A.span_tables = 0;
+    if (!A.sky || !c->span_on || A.out32 || A.spp > 1) return;
+    trt::SpanIn in{};
+    in.width = A.width;
+    in.height = A.height;
+    in.dz = A.dz;
+    in.flags = A.flags;
+    in.band_rows = A.band_rows;
+    in.band_count = A.band_count;
+    in.band_index = A.band_index;
+    in.rays_in = A.rays_in != nullptr;
+    for (int i = 0; i < 4; ++i) {
+        for (int a = 0; a < 3; ++a) in.sph[i][a] = A.sph[i].c[a];
+        in.sph[i][3] = A.sph[i].r;
+    }
+    float cams[3 * trt::kMaxLaunchFrames];
+    const uint32_t n = std::min(A.nframes, trt::kMaxLaunchFrames);
+    for (uint32_t f = 0; f < n; ++f)
+        for (int a = 0; a < 3; ++a) cams[3 * f + a] = A.fr[f].cam[a];
+    uint32_t ntr = 0, shift = 0;
+    const uint32_t T = trt::sky_spans(in, cams, n, c->span_frames, A.span, &ntr, &shift);
+    if (T == 0 || A.ntx == 0 || ntr != A.ntiles / A.ntx) return; // the kernel indexes by tile / ntx
+    A.span_tables = T;
+    A.span_shift = shift;
+    A.span_ntr = ntr;
 }
 
 int check_params(trt_ctx* c, const trt_params* p) {
@@ -1115,6 +1148,7 @@ int render_frame_list(trt_ctx* c, const trt_params* p, const FrameOut* frames, u
         fill_ubo_args(A, c->ubo);
         A.nframes = n;
         for (uint32_t k = 0; k < n; ++k) fill_frame(A.fr[k], ubo_of(i0 + k), frames[i0 + k].out8, frames[i0 + k].in_place);
+        fill_spans(c, A);
         uint32_t slot = j % nfl;
         if ((rc = prepare_split(c, p, A, slot, sv[slot])) != TRT_OK) {
             // auto count: a slot whose scratch does not fit in device memory is dropped, with the
@@ -1233,6 +1267,7 @@ int trt_render(trt_ctx* c, const trt_params* p, uint8_t* out8, float* out32, trt
         }
     }
     if (npx > 0 && (rc = attach_sky(c, A, count, c->stream)) != TRT_OK) return rc;
+    fill_spans(c, A);
     const uint32_t slot = render_slot(c, c->stream);
     c->cur_in_flight = 1u; // one frame: its latency is the rate
     if ((rc = prepare_split(c, p, A, slot, c->stream)) != TRT_OK) return rc;
