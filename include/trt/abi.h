@@ -364,6 +364,20 @@ int trt_band_plan(uint32_t width, uint32_t height, uint32_t band_rows, uint32_t 
                   uint32_t first_frame, uint32_t nframes, int root, uint32_t flags, trt_band_layout* layout,
                   trt_band_xfer* xfers, uint32_t cap, uint32_t* count);
 
+/* ---- diagnostic: the shadow occluder masks of a launch --------------------------------------
+ * Plain triangle-free frames skip a shadow query's test of sphere j for light i wherever the
+ * launch's masks prove it cannot be hit: bit 4 * i + j of a mask = "sphere j may occlude light
+ * i".  This returns the masks the runtime would build for a UBO, computed on the host (no context,
+ * no GPU).  spheres: 4 x (centre xyz, radius); lights: 3 x xyz; flags: TRT_FLAG_SPHERES is read;
+ * cell: edge of a floor cell (<= 0: the default, 0.25).  out_cells receives *nx * *nz masks, cell
+ * (ix, iz) at [iz * *nx + ix], covering floor x in [-10 + ix * cell, ...), z in [-30 + iz * cell,
+ * ...) at y = -4 (room for `cap` masks); out_rows receives the 4 masks of hits on spheres 0..3.
+ * Returns 0, or 1 when the masks are the all-ones fallback (*nx = *nz = 1: spheres off, a
+ * non-finite or absurd input, a light inside a sphere or on the floor plane), or -1 on a null
+ * argument or when the cells do not fit `cap`. */
+int trt_diag_shadow_mask(const float* spheres, const float* lights, uint32_t flags, float cell,
+                         uint16_t* out_cells, uint32_t cap, uint32_t* nx, uint32_t* nz, uint32_t* out_rows);
+
 /* ---- host scene build (main.cpp:192-252, 1529-1580, 2290-2335) -------------------- */
 
 typedef struct trt_scene trt_scene;

@@ -1,0 +1,220 @@
+"""Shadow occluder masks on the host (csrc/shadow_mask.cpp through trt_diag_shadow_mask, no GPU).
+
+Bit 4 * i + j of a mask says that sphere j may occlude light i; sky_trace_kernel skips the test of
+a sphere whose bit is clear, so a clear bit must be a proof.  The conservativeness tests restate
+sphere_hit (trt_kernel.hip) in numpy float32 for shadow queries from sampled hit points and
+assert the bit wherever sphere_hit's first branch passes (d2 <= r2) and the chord it then finds,
+[t0, t1], overlaps the query's stretch (0, |L - p|).  That is weaker than a hit needs (a hit
+needs t0 or t1 inside (1e-3, |L - p|)), so the assertion is stricter than "no hit is lost".
+
+The first branch alone, without the chord, cannot be the condition: it also passes for a sphere
+BEHIND the origin (the line, not the ray), so it is symmetric in occluder and origin sphere,
+while the masks are not and need not be: in the reference scene sphere 3 shadows spheres 0, 1
+and 2 from light 1, so the line through a point of sphere 3 towards light 1 passes through them
+behind the origin, and rows that honoured that would keep 30 of 48 bits, not the at most 26 the
+usefulness test asks for (test_first_branch_alone_is_not_the_condition shows the case).
+"""
+from __future__ import annotations
+
+import numpy as np
+import pytest
+
+from tests.shadow_mask_common import (ALL, REF_LIGHTS, REF_SPHERES, cutting_floor_scene, masks, overlapping_scene,
+                                      seeded_scene)
+from vkcomputeshader_tinyraytracer_amd import types as T
+
+F = np.float32
+EPS = F(1e-3)
+N_FLOOR = 200_000
+N_SPHERE = 50_000
+
+SCENES = {
+    "reference": lambda: (REF_SPHERES.copy(), REF_LIGHTS.copy()),
+    "seed1": lambda: seeded_scene(1),
+    "seed2": lambda: seeded_scene(2),
+    "seed3": lambda: seeded_scene(3),
+    "seed4": lambda: seeded_scene(4),
+    "cuts_floor": cutting_floor_scene,
+    "overlapping": overlapping_scene,
+}
+
+
+def _dot(a, b):
+    return (a[..., 0] * b[..., 0] + a[..., 1] * b[..., 1]) + a[..., 2] * b[..., 2]
+
+
+def query_needs(p, n, sign, sph, lts):
+    """[point, light, sphere] of float32 shadow queries from hit points p with normals n, origin
+    p + sign * n * EPS: (first branch passes and the chord overlaps (0, |L - p|), first branch)."""
+    need = np.zeros((len(p), 3, 4), bool)
+    first = np.zeros((len(p), 3, 4), bool)
+    so = (p + F(sign) * n * EPS).astype(F)
+    for i in range(3):
+        d = (lts[i][None, :] - p).astype(F)
+        dist = np.sqrt(_dot(d, d)).astype(F)
+        ld = (d / dist[:, None]).astype(F)
+        for j in range(4):
+            Lc = (sph[j, :3][None, :] - so).astype(F)
+            tca = _dot(Lc, ld).astype(F)
+            d2 = (_dot(Lc, Lc) - tca * tca).astype(F)
+            r2 = F(sph[j, 3] * sph[j, 3])
+            ok = d2 <= r2
+            thc = np.sqrt(np.where(ok, r2 - d2, F(0))).astype(F)
+            first[:, i, j] = ok
+            need[:, i, j] = ok & (tca + thc > 0) & (tca - thc < dist)
+    return need, first
+
+
+def floor_points(sph, lts, rng, n=N_FLOOR):
+    """Half uniform over the floor rectangle, half within 0.05 of a (light, sphere) shadow outline
+    (the tangent cone of the sphere from the light, cut by y = -4); y perturbed by +-1e-4."""
+    per = n // 2 // 12
+    parts = []
+    for i in range(3):
+        for j in range(4):
+            L, c, r = lts[i].astype(np.float64), sph[j, :3].astype(np.float64), float(sph[j, 3])
+            d = c - L
+            D = np.linalg.norm(d)
+            if D <= r:
+                continue
+            centre = L + d * (1 - r * r / (D * D))
+            rad = r * np.sqrt(1 - r * r / (D * D))
+            u = np.cross(d, [0.0, 1.0, 0.3])
+            u /= np.linalg.norm(u)
+            v = np.cross(d / D, u)
+            a = rng.uniform(0, 2 * np.pi, 3 * per)
+            q = centre + rad * (np.cos(a)[:, None] * u + np.sin(a)[:, None] * v)
+            s = (-4.0 - L[1]) / (q[:, 1] - L[1])
+            pt = L + s[:, None] * (q - L)
+            pt = pt[(s > 0) & np.isfinite(s)]
+            pt[:, 0] += rng.uniform(-0.05, 0.05, len(pt))
+            pt[:, 2] += rng.uniform(-0.05, 0.05, len(pt))
+            inside = (np.abs(pt[:, 0]) < 10) & (pt[:, 2] < -5) & (pt[:, 2] > -30)
+            parts.append(pt[inside][:per])
+    outline = np.concatenate(parts) if parts else np.zeros((0, 3))
+    nu = n - len(outline)
+    uni = np.stack([rng.uniform(-10, 10, nu), np.full(nu, -4.0), rng.uniform(-30, -5, nu)], 1)
+    p = np.concatenate([outline, uni])
+    p[:, 1] = -4.0 + rng.uniform(-1e-4, 1e-4, len(p))
+    p = p.astype(F)
+    keep = (np.abs(p[:, 0]) < F(10)) & (p[:, 2] < F(-5)) & (p[:, 2] > F(-30))  # scene_intersect's test
+    return p[keep], len(outline)
+
+
+def cell_masks(cells, p, cell):
+    nz, nx = cells.shape
+    inv = F(1.0 / cell)
+    ix = np.clip(((p[:, 0] + F(10)) * inv).astype(np.int32), 0, nx - 1)
+    iz = np.clip(((p[:, 2] + F(30)) * inv).astype(np.int32), 0, nz - 1)
+    return cells[iz, ix].astype(np.uint32)
+
+
+def bits(m):
+    """[..., light, sphere] booleans of masks."""
+    return ((np.asarray(m)[..., None] >> np.arange(12)) & 1).astype(bool).reshape(*np.shape(m), 3, 4)
+
+
+@pytest.mark.parametrize("cell", [0.25, 0.5])
+@pytest.mark.parametrize("name", sorted(SCENES))
+def test_floor_cells_are_conservative(name, cell):
+    sph, lts = SCENES[name]()
+    cells, _, fb = masks(sph, lts, cell=cell)
+    assert not fb, "the scene must not take the all-ones fallback"
+    p, n_outline = floor_points(sph, lts, np.random.default_rng(7))
+    assert len(p) >= N_FLOOR - 16 and n_outline > 0
+    have = bits(cell_masks(cells, p, cell))
+    n = np.broadcast_to(np.array([0, 1, 0], F), p.shape)
+    for sign in (1, -1):
+        need, _ = query_needs(p, n, sign, sph, lts)
+        assert need.any()
+        lost = need & ~have
+        assert not lost.any(), (name, cell, sign, int(lost.sum()), p[lost.any(axis=(1, 2))][:3])
+
+
+@pytest.mark.parametrize("name", sorted(SCENES))
+def test_sphere_rows_are_conservative(name):
+    sph, lts = SCENES[name]()
+    _, rows, fb = masks(sph, lts)
+    assert not fb
+    rng = np.random.default_rng(11)
+    for k in range(4):
+        u = rng.normal(size=(N_SPHERE, 3))
+        u /= np.linalg.norm(u, axis=1, keepdims=True)
+        u = u.astype(F)
+        p = (sph[k, :3][None, :] + F(sph[k, 3]) * u).astype(F)
+        d = (p - sph[k, :3][None, :]).astype(F)
+        n = (d / np.sqrt(_dot(d, d)).astype(F)[:, None]).astype(F)
+        have = bits(np.uint32(rows[k]))
+        assert have[:, k].all(), "a sphere may always occlude its own points"
+        for sign in (1, -1):
+            need, _ = query_needs(p, n, sign, sph, lts)
+            lost = need & ~have[None]
+            assert not lost.any(), (name, k, sign, np.argwhere(lost.any(axis=0)))
+
+
+def test_first_branch_alone_is_not_the_condition():
+    """The line through a point of reference sphere 3 towards light 1 passes through the other
+    spheres behind the point: the first branch passes, no hit is possible, and the row leaves the
+    bits clear (see the module docstring)."""
+    sph, lts = REF_SPHERES, REF_LIGHTS
+    _, rows, _ = masks(sph, lts)
+    rng = np.random.default_rng(3)
+    u = rng.normal(size=(N_SPHERE, 3))
+    u /= np.linalg.norm(u, axis=1, keepdims=True)
+    p = (sph[3, :3][None, :] + F(sph[3, 3]) * u.astype(F)).astype(F)
+    n = u.astype(F)
+    need, first = query_needs(p, n, 1, sph, lts)
+    have = bits(np.uint32(rows[3]))
+    assert (first & ~have[None]).any() and not (need & ~have[None]).any()
+
+
+def _assert_all_ones(sph, lts, flags=T.FLAG_SPHERES | T.FLAG_FLOOR):
+    cells, rows, fb = masks(sph, lts, flags=flags)
+    assert fb and cells.shape == (1, 1) and int(cells[0, 0]) == ALL and (rows == ALL).all()
+
+
+@pytest.mark.parametrize("bad", [float("nan"), float("inf"), float("-inf"), 1e7])
+def test_fallback_on_non_finite_or_absurd_input(bad):
+    for j in range(4):
+        for a in range(4):
+            sph = REF_SPHERES.copy()
+            sph[j, a] = bad
+            _assert_all_ones(sph, REF_LIGHTS)
+    for i in range(3):
+        for a in range(3):
+            lts = REF_LIGHTS.copy()
+            lts[i, a] = bad
+            _assert_all_ones(REF_SPHERES, lts)
+
+
+def test_fallback_on_light_inside_a_sphere():
+    lts = REF_LIGHTS.copy()
+    lts[1] = (7.0, 5.0, -15.0)  # inside sphere 3
+    _assert_all_ones(REF_SPHERES, lts)
+    lts[1] = (7.0, 5.0, -18.0 + 4.005)  # within the pad of its surface
+    _assert_all_ones(REF_SPHERES, lts)
+
+
+def test_fallback_on_light_on_the_floor_plane():
+    lts = REF_LIGHTS.copy()
+    lts[0] = (-20.0, -4.0, 20.0)
+    _assert_all_ones(REF_SPHERES, lts)
+    lts[0] = (-20.0, -4.0 + 5e-3, 20.0)
+    _assert_all_ones(REF_SPHERES, lts)
+
+
+def test_fallback_with_spheres_off():
+    _assert_all_ones(REF_SPHERES, REF_LIGHTS, flags=T.FLAG_FLOOR | T.FLAG_ENVMAP)
+
+
+def test_masks_are_useful_for_the_reference_scene():
+    """A cap that an all-ones table does not pass: the double-precision model of the construction
+    sets 8.6 % of the (cell, bit) pairs at cell 0.25 and keeps 24 of the rows' 48 bits."""
+    cells, rows, fb = masks(REF_SPHERES, REF_LIGHTS, cell=0.25)
+    assert not fb and cells.shape == (100, 80)
+    share = bits(cells.astype(np.uint32)).mean()
+    kept = int(sum(bin(int(r)).count("1") for r in rows))
+    print(f"cell bits set {100 * share:.2f} %, row bits kept {kept} of 48")
+    assert share <= 0.12
+    assert kept <= 26
+    assert all(bin(int(rows[k])).count("1") >= 3 for k in range(4))  # the self tests stay

@@ -126,6 +126,8 @@ def lib() -> ctypes.CDLL:
         "trt_band_plan": (c_int, [c_u32, c_u32, c_u32, c_u32, c_u32, c_u32, c_u32, c_int, c_u32,
                                   ctypes.POINTER(BandLayout), ctypes.POINTER(BandXfer), c_u32,
                                   ctypes.POINTER(c_u32)]),
+        "trt_diag_shadow_mask": (c_int, [f3, f3, c_u32, ctypes.c_float, ctypes.POINTER(ctypes.c_uint16), c_u32,
+                                         ctypes.POINTER(c_u32), ctypes.POINTER(c_u32), ctypes.POINTER(c_u32)]),
     }
     for name, (res, args) in sigs.items():
         fn = getattr(L, name)
@@ -195,4 +197,5 @@ ABI_SYMBOLS = (
     "trt_frame_root",
     "trt_band_frame_row",
     "trt_band_plan",
+    "trt_diag_shadow_mask",
 )

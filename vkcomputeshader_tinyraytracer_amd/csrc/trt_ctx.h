@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "../../include/trt/abi.h"
+#include "shadow_mask.h"
 #include "trt_device.h"
 
 // Frames-in-flight slots of a context: a private build-time knob (the public
@@ -58,6 +59,18 @@ struct trt_ctx {
     // table per launch)
     bool span_on = true;
     uint32_t span_frames = 16;
+    // Shadow occluder masks (KArgs::smask, shadow_mask.h) of every launch that has sky spans:
+    // d_smask holds the floor cells of smask_key's scene, rebuilt when the bytes the build reads
+    // change (the UBO's spheres and lights, the spheres flag).  smask_on: the TRT_SHADOW_MASK env
+    // knob; smask_cell: TRT_SHADOW_MASK_CELL; smask_ok: smask_key's masks are built (d_smask null:
+    // no device memory; smask_fallback: all ones — either way the frames run without masks).
+    uint16_t* d_smask = nullptr;
+    bool smask_on = true, smask_ok = false;
+    float smask_cell = trt::kShadowCellDefault;
+    trt::ShadowMaskIn smask_key{};
+    uint32_t smask_nx = 1, smask_nz = 1, smask_rows[2] = {0x0FFF0FFFu, 0x0FFF0FFFu};
+    float smask_inv = 0.0f;
+    bool smask_fallback = true;
     uint64_t env_gen = 0;
     struct SkyKey {
         uint32_t width, height, flags;

@@ -265,6 +265,14 @@ struct KArgs {
     // span_tables 0: none (always so when sky is null).
     uint32_t span_tables, span_shift, span_ntr;
     uint32_t span[kSpanWords];
+    // Shadow occluder masks (shadow_mask.h; sky_trace_kernel_smask only), or null (every sphere is
+    // tested): bit 4 * i + j of a mask = sphere j may occlude light i.  smask: smask_nx x smask_nz
+    // floor cells, cell (int((x + 10) * smask_inv), int((z + 30) * smask_inv)) clamped; smask_rows:
+    // the masks of hits on spheres 0 | 1 << 16 and 2 | 3 << 16.
+    const uint16_t* __restrict__ smask;
+    uint32_t smask_nx, smask_nz;
+    float smask_inv;
+    uint32_t smask_rows[2];
 };
 static_assert(sizeof(KArgs) <= 4096, "KArgs fits the 4 KB kernel-argument limit");
 

@@ -1048,9 +1048,15 @@ __device__ __forceinline__ void scene_intersect(const KArgs& A, f3 o, f3 d, Hit&
 }
 
 // shadow_intersect, shader.comp:364-399: any hit on spheres / triangles; floor excluded.
-template <bool COUNT, int GEOM>
+// SMASK (sky_trace_kernel_smask): bit j of the lane's `sm` says whether sphere j can occlude this
+// query's light from the lane's hit point (shadow_mask.h: a clear bit is a proof that the test
+// returns false).  A query whose four bits are clear in every lane is done after one ballot (most
+// floor tiles); otherwise a sphere whose bit is clear in every lane still in the query is not
+// tested: one ballot and a scalar branch around sphere_hit, nothing per lane.
+template <bool COUNT, int GEOM, bool SMASK = false>
 __device__ __forceinline__ bool shadow_intersect(const KArgs& A, f3 o, f3 d, float max_dist, Cnt& c,
-                                                 float4* slab) {
+                                                 float4* slab, uint32_t sm = 0xFu) {
+    static_assert(!SMASK || (GEOM == 0 && !COUNT), "the occluder masks serve plain GEOM 0 frames");
 #ifdef TRT_DIAG_NO_SHADOW
     return false; // diagnostic build only: prices the shadow rays
 #endif
@@ -1067,11 +1073,15 @@ __device__ __forceinline__ bool shadow_intersect(const KArgs& A, f3 o, f3 d, flo
         return false;
     }
 #endif
+    if constexpr (SMASK)
+        if (__ballot((sm & 0xFu) != 0u) == 0ull) return false;
     if (A.flags & TRT_FLAG_SPHERES) {
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             float t = 1e10f;
             if (COUNT) ++c.sph;
+            if constexpr (SMASK)
+                if (__ballot(((sm >> i) & 1u) != 0u) == 0ull) continue;
             if (sphere_hit(o, d, A.sph[i], t) && t < max_dist) return true;
         }
     }
@@ -1596,7 +1606,9 @@ __device__ __forceinline__ MatVals load_mat(const KArgs& A, int kind, int idx, f
 // the factored form compiles the C2 and C4 kernels with more live registers — C2 spilled.)
 // ROOT: the caller has already intersected `cur` (trace_tile's sky test) and passes its hit in
 // `root`, so the segment is not tested twice.
-template <int CAP, bool COUNT, int GEOM, bool SPLIT, bool HYB = SPLIT, bool ROOT = false>
+// SMASK: the lane looks up the occluder mask of its hit point (KArgs::smask for a floor hit, the
+// hit sphere's row otherwise) and hands each light's four bits to shadow_intersect.
+template <int CAP, bool COUNT, int GEOM, bool SPLIT, bool HYB = SPLIT, bool ROOT = false, bool SMASK = false>
 __device__ __forceinline__ f3 cast_seg(const KArgs& A, Seg cur, Cnt& cnt, float* lds, float4* slab,
                                        uint32_t pixel, bool& spilled, const Hit* root = nullptr) {
     const int D = (int)A.max_depth;
@@ -1623,7 +1635,16 @@ __device__ __forceinline__ f3 cast_seg(const KArgs& A, Seg cur, Cnt& cnt, float*
             f3 p = add(cur.o, muls(cur.d, h.t));
             f3 n;
             float alb[4], kd[3], sexp, ior;
+            uint32_t sm = 0xFFFu;
             if (h.kind == HIT_FLOOR) {
+                if constexpr (SMASK) { // issued here: the load's latency hides under the first light's terms
+                    const int ix = min(max((int)((p.x + 10.0f) * A.smask_inv), 0), (int)A.smask_nx - 1);
+                    const int iz = min(max((int)((p.z + 30.0f) * A.smask_inv), 0), (int)A.smask_nz - 1);
+                    sm = A.smask[(uint32_t)iz * A.smask_nx + (uint32_t)ix];
+#ifdef TRT_DIAG_NO_FLOOR_SHADOW
+                    sm = 0u; // diagnostic build only: prices the sphere tests of floor-hit shadow queries
+#endif
+                }
                 n = mk(0.0f, 1.0f, 0.0f);
                 float c0 = 0.3f, c1 = 0.3f, c2 = 0.3f;
                 if (A.flags & TRT_FLAG_CHECKER) { // shader.comp:312
@@ -1640,6 +1661,7 @@ __device__ __forceinline__ f3 cast_seg(const KArgs& A, Seg cur, Cnt& cnt, float*
                 ior = 1.0f;
             } else if (h.kind == HIT_SPHERE) {
                 const SphereArg& s = A.sph[h.idx];
+                if constexpr (SMASK) sm = ((h.idx < 2 ? A.smask_rows[0] : A.smask_rows[1]) >> ((h.idx & 1) * 16)) & 0xFFFu;
                 n = normalize3(sub(p, mk(s.c[0], s.c[1], s.c[2])));
 #pragma unroll
                 for (int k = 0; k < 4; ++k) alb[k] = s.m.albedo[k];
@@ -1769,7 +1791,7 @@ __device__ __forceinline__ f3 cast_seg(const KArgs& A, Seg cur, Cnt& cnt, float*
                 if (COUNT) ++cnt.sh;
                 if (!COUNT && !matters) continue;
                 const Cnt before = cnt;
-                const bool occl = shadow_intersect<COUNT, GEOM>(A, so, ld, dist, cnt, slab);
+                const bool occl = shadow_intersect<COUNT, GEOM, SMASK>(A, so, ld, dist, cnt, slab, sm >> (4 * i));
                 if (COUNT && !matters) {
                     ++cnt.sk;
                     cnt.ssph += cnt.sph - before.sph;
@@ -2243,7 +2265,8 @@ __device__ __forceinline__ void sky_tile_store(const KArgs& A, uint32_t tile, co
 // its other lanes take work from the wave's segment pool as the trees grow, so a glass tile's
 // segments are spread over more waves (a shorter frame latency) at the price of idle lanes in
 // cheap tiles.
-template <int CAP, bool COUNT, int GEOM, bool SPLIT, bool DEFER = false, bool HYB = SPLIT, bool SKY = false>
+template <int CAP, bool COUNT, int GEOM, bool SPLIT, bool DEFER = false, bool HYB = SPLIT, bool SKY = false,
+          bool SMASK = false>
 __device__ __forceinline__ void trace_tile(const KArgs& A, const FrameRec& F, uint32_t tile, Cnt& cnt, float* lds,
                                            float4* slab, uint32_t sub = 0, uint32_t frame = 0) {
     const uint32_t lane = lane_id();
@@ -2314,8 +2337,8 @@ __device__ __forceinline__ void trace_tile(const KArgs& A, const FrameRec& F, ui
                 return;
             }
             bool unused = false;
-            const f3 c = cast_seg<CAP, false, 0, false, false, true>(A, Seg{orig, d, 1.0f, 0}, cnt, lds, slab, 0u,
-                                                                     unused, &h);
+            const f3 c = cast_seg<CAP, false, 0, false, false, true, SMASK>(A, Seg{orig, d, 1.0f, 0}, cnt, lds, slab,
+                                                                           0u, unused, &h);
             store_pixel(A, F, o, mk(clamp01(c.x), clamp01(c.y), clamp01(c.z))); // cast_ray's clamp
             return;
         }
@@ -2509,9 +2532,11 @@ constexpr int trace_waves() {
     return (DEFER && GEOM == 3) ? TRT_DEFER_WAVES : waves_per_simd<GEOM, ((SPLIT || DEFER) ? 99 : CAP)>();
 }
 
-template <int CAP, bool COUNT, int GEOM, bool SPLIT, bool DEFER, bool HYB, bool SKY, bool SPANS = false>
+template <int CAP, bool COUNT, int GEOM, bool SPLIT, bool DEFER, bool HYB, bool SKY, bool SPANS = false,
+          bool SMASK = false>
 __device__ __forceinline__ void trace_body(const KArgs& A) {
     static_assert(!SPANS || SKY, "the sky spans cull into the sky table");
+    static_assert(!SMASK || SPANS, "the occluder masks ride on the span kernel");
     __shared__ float lds[DEFER ? defer_pool_floats() : lds_stack_floats<CAP, GEOM, HYB>()];
     // GEOM 1: one batch slab, 64 x (v0, e1, e2); GEOM 2: the BVH traversal stacks
     __shared__ float4 slab[slab_float4s<GEOM>()];
@@ -2553,8 +2578,8 @@ __device__ __forceinline__ void trace_body(const KArgs& A) {
                 }
             }
 #endif
-            trace_tile<CAP, COUNT, GEOM, SPLIT, DEFER, HYB, SKY>(A, A.fr[f], tile, cnt, lds, slab);
-            if (f + 1u < A.nframes) trace_tile<CAP, COUNT, GEOM, SPLIT, DEFER, HYB, SKY>(A, A.fr[f + 1u], tile, cnt, lds, slab);
+            trace_tile<CAP, COUNT, GEOM, SPLIT, DEFER, HYB, SKY, SMASK>(A, A.fr[f], tile, cnt, lds, slab);
+            if (f + 1u < A.nframes) trace_tile<CAP, COUNT, GEOM, SPLIT, DEFER, HYB, SKY, SMASK>(A, A.fr[f + 1u], tile, cnt, lds, slab);
             if (COUNT) flush_counts(A, cnt);
             return;
         } else if (A.xcd_inter) {
@@ -2614,7 +2639,7 @@ __device__ __forceinline__ void trace_body(const KArgs& A) {
         }
     }
 #endif
-    trace_tile<CAP, COUNT, GEOM, SPLIT, DEFER, HYB, SKY>(A, A.fr[f], tile, cnt, lds, slab);
+    trace_tile<CAP, COUNT, GEOM, SPLIT, DEFER, HYB, SKY, SMASK>(A, A.fr[f], tile, cnt, lds, slab);
 #ifdef TRT_DIAG_WAVE_CLOCK
     __syncthreads();
     // single-frame launches write the records to out32; multi-frame launches to the diagnostic
@@ -2651,6 +2676,15 @@ __global__ __launch_bounds__(64, (trace_waves<0, CAP, false, false>())) void sky
 template <int CAP>
 __global__ __launch_bounds__(64, (trace_waves<0, CAP, false, false>())) void sky_trace_kernel_nospan(KArgs A) {
     trace_body<CAP, false, 0, false, false, false, true, false>(A);
+}
+// sky_trace_kernel with the shadow occluder masks (A.smask set: shadow_intersect SMASK).  A kernel
+// of its own, so that a launch without masks (TRT_SHADOW_MASK=0, a scene or camera of the
+// all-ones fallback) runs sky_trace_kernel exactly as before: all-ones masks in the same kernel
+// cost it 6.6 % (profiles/shadow_mask_ab_same_kernel_summary.txt).  A launch without spans runs
+// without masks.
+template <int CAP>
+__global__ __launch_bounds__(64, (trace_waves<0, CAP, false, false>())) void sky_trace_kernel_smask(KArgs A) {
+    trace_body<CAP, false, 0, false, false, false, true, true, true>(A);
 }
 
 // One round of a split frame: persistent waves take 64 tasks at a time (static schedule) from
@@ -3034,6 +3068,7 @@ hipError_t launch_trace(const KArgs& A, hipStream_t stream, bool count) {
 #define TRT_LAUNCH_G(CAP, G)                                                                             \
     do {                                                                                                 \
         if (count) hipLaunchKernelGGL((trace_kernel<CAP, true, G, false>), fgrid, block, 0, stream, A);  \
+        else if (G == 0 && sky && A.span_tables && A.smask) hipLaunchKernelGGL((sky_trace_kernel_smask<CAP>), fgrid, block, 0, stream, A); \
         else if (G == 0 && sky && A.span_tables) hipLaunchKernelGGL((sky_trace_kernel<CAP>), fgrid, block, 0, stream, A); \
         else if (G == 0 && sky) hipLaunchKernelGGL((sky_trace_kernel_nospan<CAP>), fgrid, block, 0, stream, A); \
         else hipLaunchKernelGGL((trace_kernel<CAP, false, G, false>), fgrid, block, 0, stream, A);       \

@@ -242,6 +242,11 @@ int trt_create(trt_ctx** out, int hip_device) {
     if (const char* e = std::getenv("TRT_SKY_TABLE")) c->sky_on = std::atoi(e) != 0;
     if (const char* e = std::getenv("TRT_SKY_SPANS")) c->span_on = std::atoi(e) != 0;
     if (const char* e = std::getenv("TRT_SKY_SPAN_FRAMES")) c->span_frames = (uint32_t)std::min(64, std::max(0, std::atoi(e)));
+    if (const char* e = std::getenv("TRT_SHADOW_MASK")) c->smask_on = std::atoi(e) != 0;
+    if (const char* e = std::getenv("TRT_SHADOW_MASK_CELL")) { // floor cell edge; the build clamps it
+        const float v = (float)std::atof(e);
+        if (v > 0.0f) c->smask_cell = v;
+    }
     *out = c;
     return TRT_OK;
 }
@@ -257,6 +262,7 @@ int trt_destroy(trt_ctx* c) {
     free_scene(c);
     (void)hipFree(c->d_envp);
     (void)hipFree(c->d_sky);
+    (void)hipFree(c->d_smask);
     (void)hipFree(c->d_out8);
     (void)hipFree(c->d_out32);
     (void)hipFree(c->d_rays);
@@ -661,6 +667,71 @@ void fill_spans(const trt_ctx* c, KArgs& A) {
     A.span_tables = T;
     A.span_shift = shift;
     A.span_ntr = ntr;
+}
+
+// The shadow occluder masks of a launch (KArgs::smask, shadow_mask.h), for every launch that has
+// sky spans (the only kernel that reads them is sky_trace_kernel_smask), or null: the launch then
+// runs the kernel without masks, which tests every sphere.  The key is the bytes the build
+// reads, taken from the launch's own arguments (fill_ubo_args): the spheres' centres and radii,
+// the lights and the spheres flag.  A frame loop only compares the key; a change builds the masks
+// on the host (tools/shadow_mask_host_cost.cpp), drains the device (frames of earlier calls may
+// still read the old table on other streams, as with the sky table), uploads on `stream` and
+// waits.  A context holds ONE table.  No masks: TRT_SHADOW_MASK=0, every fallback of the build
+// (all ones), a launch with a camera outside the build's error bound (beyond kShadowCamMax, or
+// not finite), and no device memory for the table.
+int attach_smask(trt_ctx* c, KArgs& A, hipStream_t stream) {
+    A.smask = nullptr;
+    if (!A.sky || !A.span_tables || !c->smask_on) return TRT_OK;
+    trt::ShadowMaskIn key{};
+    for (int j = 0; j < 4; ++j) {
+        for (int a = 0; a < 3; ++a) key.sph[j][a] = A.sph[j].c[a];
+        key.sph[j][3] = A.sph[j].r;
+    }
+    std::memcpy(key.light, A.light, sizeof(key.light));
+    key.flags = A.flags & TRT_FLAG_SPHERES;
+    if (!c->smask_ok || std::memcmp(&key, &c->smask_key, sizeof(key)) != 0) {
+        c->smask_ok = false;
+        trt::ShadowMask m;
+        trt::shadow_mask(key, c->smask_cell, true, m);
+        constexpr size_t kCells = 200u * 250u; // kShadowCellMin over the 20 x 25 floor
+        if (m.cells.size() > kCells) trt::shadow_mask(key, c->smask_cell, false, m); // cannot happen: all ones
+        if (!m.fallback) {
+            HIP_TRY(c, hipDeviceSynchronize());
+            if (!c->d_smask) {
+                const hipError_t e = hipMalloc((void**)&c->d_smask, kCells * sizeof(uint16_t));
+                if (e == hipErrorOutOfMemory) {
+                    (void)hipGetLastError(); // not the next launch's error
+                    c->d_smask = nullptr;    // frames of this key run without masks: no retry per call
+                } else {
+                    HIP_TRY(c, e);
+                }
+            }
+            if (c->d_smask) {
+                HIP_TRY(c, hipMemcpyAsync(c->d_smask, m.cells.data(), m.cells.size() * sizeof(uint16_t),
+                                          hipMemcpyHostToDevice, stream));
+                HIP_TRY(c, hipStreamSynchronize(stream));
+            }
+        }
+        c->smask_nx = m.nx;
+        c->smask_nz = m.nz;
+        c->smask_inv = m.inv_cell;
+        c->smask_rows[0] = m.rows[0] | (m.rows[1] << 16);
+        c->smask_rows[1] = m.rows[2] | (m.rows[3] << 16);
+        c->smask_fallback = m.fallback;
+        c->smask_key = key;
+        c->smask_ok = true;
+    }
+    if (!c->d_smask || c->smask_fallback) return TRT_OK;
+    for (uint32_t f = 0; f < A.nframes && f < trt::kMaxLaunchFrames; ++f)
+        for (int a = 0; a < 3; ++a)
+            if (!(std::fabs(A.fr[f].cam[a]) <= trt::kShadowCamMax)) return TRT_OK; // NaN too
+    A.smask = c->d_smask;
+    A.smask_nx = c->smask_nx;
+    A.smask_nz = c->smask_nz;
+    A.smask_inv = c->smask_inv;
+    A.smask_rows[0] = c->smask_rows[0];
+    A.smask_rows[1] = c->smask_rows[1];
+    return TRT_OK;
 }
 
 int check_params(trt_ctx* c, const trt_params* p) {
@@ -1149,6 +1220,7 @@ int render_frame_list(trt_ctx* c, const trt_params* p, const FrameOut* frames, u
         A.nframes = n;
         for (uint32_t k = 0; k < n; ++k) fill_frame(A.fr[k], ubo_of(i0 + k), frames[i0 + k].out8, frames[i0 + k].in_place);
         fill_spans(c, A);
+        if ((rc = attach_smask(c, A, c->stream)) != TRT_OK) return rc;
         uint32_t slot = j % nfl;
         if ((rc = prepare_split(c, p, A, slot, sv[slot])) != TRT_OK) {
             // auto count: a slot whose scratch does not fit in device memory is dropped, with the
@@ -1268,6 +1340,7 @@ int trt_render(trt_ctx* c, const trt_params* p, uint8_t* out8, float* out32, trt
     }
     if (npx > 0 && (rc = attach_sky(c, A, count, c->stream)) != TRT_OK) return rc;
     fill_spans(c, A);
+    if ((rc = attach_smask(c, A, c->stream)) != TRT_OK) return rc;
     const uint32_t slot = render_slot(c, c->stream);
     c->cur_in_flight = 1u; // one frame: its latency is the rate
     if ((rc = prepare_split(c, p, A, slot, c->stream)) != TRT_OK) return rc;
