@@ -49,6 +49,7 @@ for v in "$@"; do
         dumpshadow) variant dumpshadow -DTRT_DIAG_DUMP_SHADOW ;;
         noshadow) variant noshadow -DTRT_DIAG_NO_SHADOW ;;
         nofloorshadow) variant nofloorshadow -DTRT_DIAG_NO_FLOOR_SHADOW ;; # floor hits skip every sphere test
+        floorsky) variant floorsky -DTRT_DIAG_FLOOR_SKY ;; # floor-class tiles store their sky words: prices the class
         nopow) variant nopow -DTRT_DIAG_NO_POW ;;
         trivial) variant trivial -DTRT_DIAG_TRIVIAL ;;
         noenvfetch) variant noenvfetch -DTRT_DIAG_NO_ENV_FETCH ;;

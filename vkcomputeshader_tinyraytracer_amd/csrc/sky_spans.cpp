@@ -87,6 +87,19 @@ struct Group {
 
 constexpr double kHuge = 1e6;
 
+// std::floor / std::ceil of a double, value for value (but for the sign of a zero result), without
+// the library call: a row takes eight of them, once the sphere interval is rounded beside the span.
+inline double floor_d(double x) {
+    if (!(std::fabs(x) < 4e15)) return std::floor(x); // already an integer, or not finite
+    const double t = (double)(int64_t)x;
+    return t > x ? t - 1.0 : t;
+}
+inline double ceil_d(double x) {
+    if (!(std::fabs(x) < 4e15)) return std::ceil(x);
+    const double t = (double)(int64_t)x;
+    return t < x ? t + 1.0 : t;
+}
+
 bool finite3(const float* v) { return std::isfinite(v[0]) && std::isfinite(v[1]) && std::isfinite(v[2]); }
 
 void prepare_group(const SpanIn& in, const float* cams, uint32_t n, Group& G) {
@@ -199,7 +212,7 @@ void seg_extent(const Seg2& s, double dy_lo, double dy_hi, Range& r) {
 } // namespace
 
 uint32_t sky_spans(const SpanIn& in, const float* cams, uint32_t nframes, uint32_t group_frames, uint32_t* out,
-                   uint32_t* ntr_out, uint32_t* shift_out) {
+                   uint32_t* ntr_out, uint32_t* shift_out, uint32_t* sph_out) {
     *ntr_out = 0;
     *shift_out = 0;
     const bool banded = in.band_rows != 0 && in.band_count > 1;
@@ -221,6 +234,7 @@ uint32_t sky_spans(const SpanIn& in, const float* cams, uint32_t nframes, uint32
     const double W = (double)in.width, H = (double)in.height;
     for (uint32_t g = 0; g < T; ++g) {
         uint32_t* tab = out + (size_t)g * ntr;
+        uint32_t* stab = sph_out ? sph_out + (size_t)g * ntr : nullptr;
         const uint32_t f0 = g << shift, n = std::min(nframes - f0, 1u << shift);
         Group G;
         if (sane) prepare_group(in, cams + 3 * (size_t)f0, n, G);
@@ -228,6 +242,7 @@ uint32_t sky_spans(const SpanIn& in, const float* cams, uint32_t nframes, uint32
         for (uint32_t tr = 0; tr < ntr; ++tr) {
             if (G.full) {
                 tab[tr] = kSpanFull;
+                if (stab) stab[tr] = kSpanFull;
                 continue;
             }
             const uint32_t k0 = tr * 8u, k1 = std::min(k0 + 7u, rows - 1u);
@@ -238,18 +253,27 @@ uint32_t sky_spans(const SpanIn& in, const float* cams, uint32_t nframes, uint32
             // the last column under ROW_QUIRK, and one tile of padding
             const double dy_hi = H * 0.5 - (double)y0 + 8.0;
             const double dy_lo = H * 0.5 - (double)(y1 + 1u) - ((in.flags & TRT_FLAG_ROW_QUIRK) ? 1.0 : 0.0) - 8.0;
-            Range r;
-            for (int i = 0; i < G.nball; ++i) G.ball[i].extent(dy_lo, dy_hi, r);
+            // the balls alone first (the sphere interval), then the floor box's edges on top
+            Range rb;
+            for (int i = 0; i < G.nball; ++i) G.ball[i].extent(dy_lo, dy_hi, rb);
+            Range r = rb;
             for (int i = 0; i < G.nseg; ++i) seg_extent(G.seg[i], dy_lo, dy_hi, r);
-            if (!(r.lo <= r.hi)) {
-                tab[tr] = (r.lo == 1e300 && r.hi == -1e300) ? 0u : kSpanFull; // empty, or NaN: full
-                continue;
-            }
             // dx = x + 0.5 - W / 2; the pixel columns the extent touches, then one tile of padding
-            const double x0 = std::floor(r.lo + W * 0.5 - 0.5), x1 = std::ceil(r.hi + W * 0.5 - 0.5);
-            const double c0 = std::max(0.0, std::floor(x0 / 8.0) - 1.0);
-            const double c1 = std::min((double)ntx, std::floor(x1 / 8.0) + 2.0);
-            tab[tr] = c0 < c1 ? ((uint32_t)c0 | ((uint32_t)c1 << 16)) : 0u;
+            auto word = [&](const Range& e) -> uint32_t {
+                if (!(e.lo <= e.hi)) return (e.lo == 1e300 && e.hi == -1e300) ? 0u : kSpanFull; // empty, or NaN: full
+                const double x0 = floor_d(e.lo + W * 0.5 - 0.5), x1 = ceil_d(e.hi + W * 0.5 - 0.5);
+                const double c0 = std::max(0.0, floor_d(x0 * 0.125) - 1.0);
+                const double c1 = std::min((double)ntx, floor_d(x1 * 0.125) + 2.0);
+                return c0 < c1 ? ((uint32_t)c0 | ((uint32_t)c1 << 16)) : 0u;
+            };
+            tab[tr] = word(r);
+            if (stab) {
+                // rb lies inside r, so the interval lies inside the span; a full interval beside a
+                // span that is not full cannot arise, and would be cut to the span (still a proof).
+                // A row the floor box adds nothing to has the span's own word.
+                const uint32_t w = (rb.lo == r.lo && rb.hi == r.hi) ? tab[tr] : word(rb);
+                stab[tr] = (w == kSpanFull && tab[tr] != kSpanFull) ? tab[tr] : w;
+            }
         }
     }
     return T;
@@ -257,14 +281,14 @@ uint32_t sky_spans(const SpanIn& in, const float* cams, uint32_t nframes, uint32
 
 } // namespace trt
 
-// Diagnostic entry (not in include/trt/abi.h, like trt_diag_set_buffer): the span tables of one
-// launch, computed without a context or a GPU.  `spheres`: 4 x (centre, radius); `cams`: 3 floats
-// per frame; `out`: room for out_cap words.  Returns the number of tables (0: spans off), or -1
-// when they do not fit out_cap.
-extern "C" int trt_diag_sky_spans(uint32_t width, uint32_t height, float fov, uint32_t flags, uint32_t band_rows,
-                                  uint32_t band_count, uint32_t band_index, int rays_in, const float* spheres,
-                                  const float* cams, uint32_t nframes, uint32_t group_frames, uint32_t* out,
-                                  uint32_t out_cap, uint32_t* ntr, uint32_t* shift) {
+// Diagnostic entries (not in include/trt/abi.h, like trt_diag_set_buffer): the span tables, or the
+// sphere intervals, of one launch, computed without a context or a GPU.  `spheres`: 4 x (centre,
+// radius); `cams`: 3 floats per frame; `out`: room for out_cap words.  Return the number of tables
+// (0: spans off), or -1 when they do not fit out_cap.
+static int diag_spans(bool sphere, uint32_t width, uint32_t height, float fov, uint32_t flags, uint32_t band_rows,
+                      uint32_t band_count, uint32_t band_index, int rays_in, const float* spheres, const float* cams,
+                      uint32_t nframes, uint32_t group_frames, uint32_t* out, uint32_t out_cap, uint32_t* ntr,
+                      uint32_t* shift) {
     if (!spheres || !cams || !out || !ntr || !shift) return -1;
     trt::SpanIn in{};
     in.width = width;
@@ -277,9 +301,27 @@ extern "C" int trt_diag_sky_spans(uint32_t width, uint32_t height, float fov, ui
     in.rays_in = rays_in != 0;
     for (int i = 0; i < 4; ++i)
         for (int a = 0; a < 4; ++a) in.sph[i][a] = spheres[4 * i + a];
-    uint32_t tmp[trt::kSpanWords];
-    const uint32_t T = trt::sky_spans(in, cams, nframes, group_frames, tmp, ntr, shift);
+    uint32_t tmp[trt::kSpanWords], stmp[trt::kSpanWords];
+    const uint32_t T = trt::sky_spans(in, cams, nframes, group_frames, tmp, ntr, shift, stmp);
     if ((size_t)T * *ntr > out_cap) return -1;
-    std::copy(tmp, tmp + (size_t)T * *ntr, out);
+    const uint32_t* src = sphere ? stmp : tmp;
+    std::copy(src, src + (size_t)T * *ntr, out);
     return (int)T;
+}
+
+extern "C" int trt_diag_sky_spans(uint32_t width, uint32_t height, float fov, uint32_t flags, uint32_t band_rows,
+                                  uint32_t band_count, uint32_t band_index, int rays_in, const float* spheres,
+                                  const float* cams, uint32_t nframes, uint32_t group_frames, uint32_t* out,
+                                  uint32_t out_cap, uint32_t* ntr, uint32_t* shift) {
+    return diag_spans(false, width, height, fov, flags, band_rows, band_count, band_index, rays_in, spheres, cams, nframes,
+                      group_frames, out, out_cap, ntr, shift);
+}
+
+// The sphere intervals (sky_spans' sph_out) in the span words' format, s0 | s1 << 16.
+extern "C" int trt_diag_sphere_spans(uint32_t width, uint32_t height, float fov, uint32_t flags, uint32_t band_rows,
+                                     uint32_t band_count, uint32_t band_index, int rays_in, const float* spheres,
+                                     const float* cams, uint32_t nframes, uint32_t group_frames, uint32_t* out,
+                                     uint32_t out_cap, uint32_t* ntr, uint32_t* shift) {
+    return diag_spans(true, width, height, fov, flags, band_rows, band_count, band_index, rays_in, spheres, cams, nframes,
+                      group_frames, out, out_cap, ntr, shift);
 }

@@ -4,7 +4,8 @@
 // Which screen regions a primary ray can hit depends on the UBOs alone, and the host holds the
 // UBO of every frame of a launch before it enqueues it.  sky_trace_kernel reads the row's
 // interval with a scalar load and stores a tile outside it straight from the sky table, without
-// generating or intersecting its primary rays.
+// generating or intersecting its primary rays.  A second interval per row,
+// of the spheres alone, marks the tiles inside the span that can only hit the floor (item 21).
 #pragma once
 
 #include <stdint.h>
@@ -34,7 +35,23 @@ struct SpanIn {
 // launch without them — for replayed rays, band_rows that are no multiple of 8 and more tile
 // rows than fit.  A group whose cameras are not finite, inside a padded sphere or not above the
 // padded floor slab gets full rows.
+//
+// `sph_out` (optional, laid out like `out`): the sphere interval of each row, s0 | s1 << 16 — the
+// same construction over the inflated balls alone, without the floor box.  Outside [s0, s1) no
+// primary ray of any frame of the table's group passes sphere_hit for any sphere, so a tile inside
+// the span and outside the interval can only hit the floor (the floor class).
+// [s0, s1) lies inside [c0, c1); it is kSpanFull wherever the span is, and empty (0) with
+// TRT_FLAG_SPHERES clear.
 uint32_t sky_spans(const SpanIn& in, const float* cams, uint32_t nframes, uint32_t group_frames, uint32_t* out,
-                   uint32_t* ntr, uint32_t* shift);
+                   uint32_t* ntr, uint32_t* shift, uint32_t* sph_out = nullptr);
+
+// The floor-class kernel's span word (KArgs::span of a launch with KArgs::floor_class set; tile
+// rows of at most 255 tiles): c0 | c1 << 8 | s0 << 16 | s1 << 24.
+constexpr uint32_t kFloorPackMaxNtx = 255;
+constexpr uint32_t kFloorPackFull = 0xff00ff00u; // [0, 255) twice: every column may hit a sphere
+inline uint32_t floor_pack(uint32_t span, uint32_t sph) {
+    auto b = [](uint32_t v) { return v < 255u ? v : 255u; };
+    return b(span & 0xffffu) | b(span >> 16) << 8 | b(sph & 0xffffu) << 16 | b(sph >> 16) << 24;
+}
 
 } // namespace trt

@@ -59,6 +59,11 @@ struct trt_ctx {
     // table per launch)
     bool span_on = true;
     uint32_t span_frames = 16;
+    // Floor class (KArgs::floor_class, sky_trace_kernel_floor) of every launch that has spans and
+    // masks.  floor_on: the TRT_FLOOR_CLASS env knob; sph_span: the sphere intervals of the launch
+    // being prepared (fill_spans writes them, attach_floor_class packs them into KArgs::span).
+    bool floor_on = true;
+    uint32_t sph_span[trt::kSpanWords] = {};
     // Shadow occluder masks (KArgs::smask, shadow_mask.h) of every launch that has sky spans:
     // d_smask holds the floor cells of smask_key's scene, rebuilt when the bytes the build reads
     // change (the UBO's spheres and lights, the spheres flag).  smask_on: the TRT_SHADOW_MASK env

@@ -273,6 +273,10 @@ struct KArgs {
     uint32_t smask_nx, smask_nz;
     float smask_inv;
     uint32_t smask_rows[2];
+    // Floor class (sky_trace_kernel_floor only; needs span_tables, smask, ntx <= 255, nframes >= 2): `span`
+    // holds floor_pack words, c0 | c1 << 8 | s0 << 16 | s1 << 24 — a tile inside [c0, c1) and
+    // outside the sphere interval [s0, s1) can only hit the floor.  0: `span` as above.
+    uint32_t floor_class;
 };
 static_assert(sizeof(KArgs) <= 4096, "KArgs fits the 4 KB kernel-argument limit");
 

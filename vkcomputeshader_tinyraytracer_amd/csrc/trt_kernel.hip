@@ -2257,6 +2257,99 @@ __device__ __forceinline__ void sky_tile_store(const KArgs& A, uint32_t tile, co
     if (F1 && F1->out8) F1->out8[out_index(A, *F1, o)] = word;
 }
 
+// Floor class (sky_trace_kernel_floor, KArgs::floor_class): the launch's span words are
+// floor_pack words, c0 | c1 << 8 | s0 << 16 | s1 << 24 (sky_spans.h).
+__device__ __forceinline__ uint32_t floor_span_word(const KArgs& A, uint32_t tile, uint32_t f) {
+    if (tile >= A.ntiles) return kFloorPackFull;
+    return A.span[(f >> A.span_shift) * A.span_ntr + tile / A.ntx];
+}
+__device__ __forceinline__ bool floor_span_outside(uint32_t col, uint32_t w) {
+    return col < (w & 0xffu) || col >= ((w >> 8) & 0xffu);
+}
+__device__ __forceinline__ bool floor_sphere_outside(uint32_t col, uint32_t w) {
+    return col < ((w >> 16) & 0xffu) || col >= (w >> 24);
+}
+
+// One frame of a floor-class tile: a tile inside its row's span and outside its sphere interval,
+// so no primary ray of it passes sphere_hit and the only primary hit is the floor.  This is
+// trace_tile's SKY path for such a lane, term for term and in the same order, without what a
+// floor hit never uses: scene_intersect's floor test alone, then cast_seg's HIT_FLOOR branch with
+// alb = {2, 0, 0, 0} (no specular term, no children, so no loop and no stack).  A lane that
+// misses is a primary miss: its pixel is its sky-table word.
+__device__ __forceinline__ void floor_frame(const KArgs& A, const FrameRec& F, f3 d, uint32_t word, size_t o, Cnt& cnt,
+                                            float4* slab) {
+    const f3 orig = mk(F.cam[0], F.cam[1], F.cam[2]);
+    float t = 1e10f;
+    bool hit = false;
+    if (A.flags & TRT_FLAG_FLOOR) { // scene_intersect's floor test (shader.comp:302-320)
+        if (fabsf(d.y) > TRT_EPS) {
+            const float tf = div_rn(-(orig.y + 4.0f), d.y);
+            if (tf > TRT_EPS && tf < t) {
+                const f3 pf = add(orig, muls(d, tf));
+                if (fabsf(pf.x) < 10.0f && pf.z < -5.0f && pf.z > -30.0f) {
+                    t = tf;
+                    hit = true;
+                }
+            }
+        }
+    }
+    if (!hit) {
+        if (F.out8) F.out8[out_index(A, F, o)] = word;
+        return;
+    }
+    const f3 p = add(orig, muls(d, t));
+    const int ix = min(max((int)((p.x + 10.0f) * A.smask_inv), 0), (int)A.smask_nx - 1);
+    const int iz = min(max((int)((p.z + 30.0f) * A.smask_inv), 0), (int)A.smask_nz - 1);
+    uint32_t sm = A.smask[(uint32_t)iz * A.smask_nx + (uint32_t)ix];
+#ifdef TRT_DIAG_NO_FLOOR_SHADOW
+    sm = 0u;
+#endif
+    const f3 n = mk(0.0f, 1.0f, 0.0f);
+    float c1 = 0.3f, c2 = 0.3f;
+    if (A.flags & TRT_FLAG_CHECKER) { // shader.comp:312
+        const float m = floorf(p.x * 0.5f + 1024.0f) + floorf(p.z * 0.5f);
+        const float mod2 = m - 2.0f * floorf(m / 2.0f);
+        if (!(mod2 == 0.0f)) {
+            c1 = 0.2f;
+            c2 = 0.1f;
+        }
+    }
+    const float alb0 = 2.0f, alb1 = 0.0f;
+    const f3 kdv = mk(0.3f, c1, c2);
+    f3 diffuse = mk(0.0f, 0.0f, 0.0f);
+    const f3 specular = mk(0.0f, 0.0f, 0.0f);
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+        const f3 L = mk(A.light[i][0], A.light[i][1], A.light[i][2]);
+        float dist;
+        const f3 ld = normalize_len3(sub(L, p), dist);
+        const f3 so = dot3(ld, n) < 0.0f ? sub(p, muls(n, TRT_EPS)) : add(p, muls(n, TRT_EPS));
+        const float diff = 1.0f * fmaxf(0.0f, dot3(n, ld));
+        const bool matters = TRT_SKIP_DARK == 0 || diff != 0.0f; // alb0 != 0, alb1 == 0
+        if (!matters) continue;
+        if (shadow_intersect<false, 0, true>(A, so, ld, dist, cnt, slab, sm >> (4 * i))) continue;
+        diffuse = add(diffuse, muls(kdv, diff));
+    }
+    // cast_seg: color = 0 + (diffuse * alb0 + specular * alb1) * thr, thr = 1
+    const f3 c = add(mk(0.0f, 0.0f, 0.0f), muls(add(muls(diffuse, alb0), muls(specular, alb1)), 1.0f));
+    store_pixel(A, F, o, mk(clamp01(c.x), clamp01(c.y), clamp01(c.z))); // cast_ray's clamp
+}
+
+// A floor-class tile in F0 and, for a frame pair, in F1: the primary direction (the camera only
+// translates, so it is the same in both frames) and the sky word once per wave.
+__device__ __forceinline__ void floor_tile(const KArgs& A, uint32_t tile, const FrameRec& F0, const FrameRec* F1, Cnt& cnt,
+                                           float4* slab) {
+    const uint32_t lane = lane_id();
+    const uint32_t x = (tile % A.ntx) * 8u + (lane & 7u), k = (tile / A.ntx) * 8u + (lane >> 3);
+    if (x >= A.width || k >= A.rows) return;
+    const uint32_t y = band_row(A, k);
+    const size_t o = (size_t)k * A.width + x;
+    const f3 d = primary_dir(A, x, y, 0);
+    const uint32_t word = A.sky[(size_t)y * A.width + x];
+    floor_frame(A, F0, d, word, o, cnt, slab);
+    if (F1) floor_frame(A, *F1, d, word, o, cnt, slab);
+}
+
 // One 8x8 pixel tile of compact output rows: the wave's 64 lanes, one pixel each.  SPLIT
 // (spp == 1 only): a pixel whose tree handed subtrees to the task queue parks its partial
 // colour in A.acc and is finished by finalize_spilled.
@@ -2533,10 +2626,11 @@ constexpr int trace_waves() {
 }
 
 template <int CAP, bool COUNT, int GEOM, bool SPLIT, bool DEFER, bool HYB, bool SKY, bool SPANS = false,
-          bool SMASK = false>
+          bool SMASK = false, bool FLOORC = false>
 __device__ __forceinline__ void trace_body(const KArgs& A) {
     static_assert(!SPANS || SKY, "the sky spans cull into the sky table");
     static_assert(!SMASK || SPANS, "the occluder masks ride on the span kernel");
+    static_assert(!FLOORC || SMASK, "the floor class rides on the mask kernel");
     __shared__ float lds[DEFER ? defer_pool_floats() : lds_stack_floats<CAP, GEOM, HYB>()];
     // GEOM 1: one batch slab, 64 x (v0, e1, e2); GEOM 2: the BVH traversal stacks
     __shared__ float4 slab[slab_float4s<GEOM>()];
@@ -2571,7 +2665,22 @@ __device__ __forceinline__ void trace_body(const KArgs& A) {
             tile = inter_tile(A, vb, pr, (A.nframes + 1u) / 2u);
             f = 2u * pr;
 #ifndef TRT_DIAG_TRIVIAL
-            if constexpr (SPANS) { // a pair never straddles two span tables (span_shift >= 1)
+            if constexpr (FLOORC) { // a pair never straddles two span tables (span_shift >= 1)
+                const uint32_t w = floor_span_word(A, tile, f), col = tile % A.ntx;
+                const FrameRec* F1 = f + 1u < A.nframes ? &A.fr[f + 1u] : nullptr;
+                if (floor_span_outside(col, w)) {
+                    sky_tile_store(A, tile, A.fr[f], F1);
+                    return;
+                }
+                if (floor_sphere_outside(col, w)) { // never for tile >= ntiles: its word is full
+#ifdef TRT_DIAG_FLOOR_SKY
+                    sky_tile_store(A, tile, A.fr[f], F1); // diagnostic build only: prices the floor class
+#else
+                    floor_tile(A, tile, A.fr[f], F1, cnt, slab);
+#endif
+                    return;
+                }
+            } else if constexpr (SPANS) {
                 if (span_outside(A, tile, span_word(A, tile, f))) {
                     sky_tile_store(A, tile, A.fr[f], f + 1u < A.nframes ? &A.fr[f + 1u] : nullptr);
                     return;
@@ -2632,7 +2741,21 @@ __device__ __forceinline__ void trace_body(const KArgs& A) {
         tile = xcd_tile(A, t);
     }
 #if !defined(TRT_DIAG_TRIVIAL) && !defined(TRT_DIAG_WAVE_CLOCK)
-    if constexpr (SPANS) {
+    if constexpr (FLOORC) {
+        const uint32_t w = floor_span_word(A, tile, f), col = tile % A.ntx;
+        if (floor_span_outside(col, w)) {
+            sky_tile_store(A, tile, A.fr[f], nullptr);
+            return;
+        }
+        if (floor_sphere_outside(col, w)) { // never for tile >= ntiles: its word is full
+#ifdef TRT_DIAG_FLOOR_SKY
+            sky_tile_store(A, tile, A.fr[f], nullptr);
+#else
+            floor_tile(A, tile, A.fr[f], nullptr, cnt, slab);
+#endif
+            return;
+        }
+    } else if constexpr (SPANS) {
         if (span_outside(A, tile, span_word(A, tile, f))) {
             sky_tile_store(A, tile, A.fr[f], nullptr);
             return;
@@ -2685,6 +2808,15 @@ __global__ __launch_bounds__(64, (trace_waves<0, CAP, false, false>())) void sky
 template <int CAP>
 __global__ __launch_bounds__(64, (trace_waves<0, CAP, false, false>())) void sky_trace_kernel_smask(KArgs A) {
     trace_body<CAP, false, 0, false, false, false, true, true, true>(A);
+}
+
+// sky_trace_kernel_smask with the floor class (A.floor_class set: the span words carry the rows'
+// sphere intervals): a tile inside its span and outside its sphere interval runs floor_tile, not
+// trace_tile.  A kernel of its own for the same reason: every launch without the class
+// (TRT_FLOOR_CLASS=0, no spans or masks, rows of more than 255 tiles) runs the kernel it ran before.
+template <int CAP>
+__global__ __launch_bounds__(64, (trace_waves<0, CAP, false, false>())) void sky_trace_kernel_floor(KArgs A) {
+    trace_body<CAP, false, 0, false, false, false, true, true, true, true>(A);
 }
 
 // One round of a split frame: persistent waves take 64 tasks at a time (static schedule) from
@@ -3068,6 +3200,7 @@ hipError_t launch_trace(const KArgs& A, hipStream_t stream, bool count) {
 #define TRT_LAUNCH_G(CAP, G)                                                                             \
     do {                                                                                                 \
         if (count) hipLaunchKernelGGL((trace_kernel<CAP, true, G, false>), fgrid, block, 0, stream, A);  \
+        else if (G == 0 && sky && A.span_tables && A.smask && A.floor_class) hipLaunchKernelGGL((sky_trace_kernel_floor<CAP>), fgrid, block, 0, stream, A); \
         else if (G == 0 && sky && A.span_tables && A.smask) hipLaunchKernelGGL((sky_trace_kernel_smask<CAP>), fgrid, block, 0, stream, A); \
         else if (G == 0 && sky && A.span_tables) hipLaunchKernelGGL((sky_trace_kernel<CAP>), fgrid, block, 0, stream, A); \
         else if (G == 0 && sky) hipLaunchKernelGGL((sky_trace_kernel_nospan<CAP>), fgrid, block, 0, stream, A); \

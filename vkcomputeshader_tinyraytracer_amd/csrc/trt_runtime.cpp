@@ -243,6 +243,7 @@ int trt_create(trt_ctx** out, int hip_device) {
     if (const char* e = std::getenv("TRT_SKY_SPANS")) c->span_on = std::atoi(e) != 0;
     if (const char* e = std::getenv("TRT_SKY_SPAN_FRAMES")) c->span_frames = (uint32_t)std::min(64, std::max(0, std::atoi(e)));
     if (const char* e = std::getenv("TRT_SHADOW_MASK")) c->smask_on = std::atoi(e) != 0;
+    if (const char* e = std::getenv("TRT_FLOOR_CLASS")) c->floor_on = std::atoi(e) != 0;
     if (const char* e = std::getenv("TRT_SHADOW_MASK_CELL")) { // floor cell edge; the build clamps it
         const float v = (float)std::atof(e);
         if (v > 0.0f) c->smask_cell = v;
@@ -641,8 +642,9 @@ int attach_sky(trt_ctx* c, KArgs& A, bool count, hipStream_t stream) {
 // The sky spans of a launch (KArgs::span), from what the launch's arguments already hold: the
 // frames' cameras (fill_frame), the UBO's spheres (fill_ubo_args) and the sky table (attach_sky).
 // Unset wherever there is no table, and under TRT_SKY_SPANS=0.
-void fill_spans(const trt_ctx* c, KArgs& A) {
+void fill_spans(trt_ctx* c, KArgs& A) {
     A.span_tables = 0;
+    A.floor_class = 0;
     if (!A.sky || !c->span_on || A.out32 || A.spp > 1) return;
     trt::SpanIn in{};
     in.width = A.width;
@@ -662,7 +664,7 @@ void fill_spans(const trt_ctx* c, KArgs& A) {
     for (uint32_t f = 0; f < n; ++f)
         for (int a = 0; a < 3; ++a) cams[3 * f + a] = A.fr[f].cam[a];
     uint32_t ntr = 0, shift = 0;
-    const uint32_t T = trt::sky_spans(in, cams, n, c->span_frames, A.span, &ntr, &shift);
+    const uint32_t T = trt::sky_spans(in, cams, n, c->span_frames, A.span, &ntr, &shift, c->floor_on && A.nframes > 1u ? c->sph_span : nullptr);
     if (T == 0 || A.ntx == 0 || ntr != A.ntiles / A.ntx) return; // the kernel indexes by tile / ntx
     A.span_tables = T;
     A.span_shift = shift;
@@ -732,6 +734,22 @@ int attach_smask(trt_ctx* c, KArgs& A, hipStream_t stream) {
     A.smask_rows[0] = c->smask_rows[0];
     A.smask_rows[1] = c->smask_rows[1];
     return TRT_OK;
+}
+
+// The floor class of a launch (KArgs::floor_class, sky_trace_kernel_floor): for every launch that
+// has spans (fill_spans, which left the rows' sphere intervals in c->sph_span) and masks
+// (attach_smask), both scene parts on and tile rows that fit the packed word, A.span is repacked
+// with the sphere interval beside the span.  Any other launch, and every launch under
+// TRT_FLOOR_CLASS=0, keeps its span words and runs the kernel it ran before.  So does a launch of
+// one frame: frames launched one by one were 1.5-2.2 % slower with the class than without
+// (profiles/floor_class_ab_summary.txt), so they neither compute the intervals nor change kernel.
+void attach_floor_class(const trt_ctx* c, KArgs& A) {
+    A.floor_class = 0;
+    if (!c->floor_on || A.nframes < 2u || !A.span_tables || !A.smask || A.ntx > trt::kFloorPackMaxNtx) return;
+    if (!(A.flags & TRT_FLAG_FLOOR) || !(A.flags & TRT_FLAG_SPHERES)) return;
+    const uint32_t words = A.span_tables * A.span_ntr;
+    for (uint32_t i = 0; i < words; ++i) A.span[i] = trt::floor_pack(A.span[i], c->sph_span[i]);
+    A.floor_class = 1;
 }
 
 int check_params(trt_ctx* c, const trt_params* p) {
@@ -1221,6 +1239,7 @@ int render_frame_list(trt_ctx* c, const trt_params* p, const FrameOut* frames, u
         for (uint32_t k = 0; k < n; ++k) fill_frame(A.fr[k], ubo_of(i0 + k), frames[i0 + k].out8, frames[i0 + k].in_place);
         fill_spans(c, A);
         if ((rc = attach_smask(c, A, c->stream)) != TRT_OK) return rc;
+        attach_floor_class(c, A);
         uint32_t slot = j % nfl;
         if ((rc = prepare_split(c, p, A, slot, sv[slot])) != TRT_OK) {
             // auto count: a slot whose scratch does not fit in device memory is dropped, with the
@@ -1341,6 +1360,7 @@ int trt_render(trt_ctx* c, const trt_params* p, uint8_t* out8, float* out32, trt
     if (npx > 0 && (rc = attach_sky(c, A, count, c->stream)) != TRT_OK) return rc;
     fill_spans(c, A);
     if ((rc = attach_smask(c, A, c->stream)) != TRT_OK) return rc;
+    attach_floor_class(c, A);
     const uint32_t slot = render_slot(c, c->stream);
     c->cur_in_flight = 1u; // one frame: its latency is the rate
     if ((rc = prepare_split(c, p, A, slot, c->stream)) != TRT_OK) return rc;
