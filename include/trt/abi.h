@@ -35,7 +35,7 @@
 extern "C" {
 #endif
 
-#define TRT_ABI_VERSION 4
+#define TRT_ABI_VERSION 5
 
 /* status codes */
 #define TRT_OK 0
@@ -239,6 +239,49 @@ int trt_defer_stats(trt_ctx* ctx, uint32_t slot, uint64_t out[5]);
 int trt_render_frames(trt_ctx* ctx, const trt_params* p, const trt_ubo* ubos, uint32_t nframes,
                       uint8_t* out_rgba8, size_t frame_stride, uint32_t time_every);
 
+/* ---- camera orientation: a view basis for the primary rays --------------------------------
+ * The reference keeps cameraFront / cameraUp (main.cpp:342-344) but only moves camPos with them:
+ * its ray table is built once for a camera looking down -z (main.cpp:1496-1506).  A view turns
+ * the camera: `right`, `up`, `back` are the columns of the camera-to-world rotation (back =
+ * -front); the reference camera is right (1,0,0), up (0,1,0), back (0,0,1).  A pixel's (and, at
+ * spp > 1, a sample's) direction under a view is, in this order,
+ *   1. c = normalize(dx, dy, dz), the host direction of main.cpp:1504 (row quirk and jitter as
+ *      without a view);
+ *   2. w[a] = (c.x * right[a] + c.y * up[a]) + c.z * back[a], a = 0, 1, 2 — every product and sum
+ *      rounded to FP32 on its own, no FMA: what a host would store into binding 1;
+ *   3. d = normalize(w), the shader's own normalize (shader.comp:593).
+ * The basis need not be orthonormal, only finite (step 3 fixes the length).  trt_params.rays_in,
+ * when set, wins over a view (the directions are the caller's).  A view whose 36 bytes equal the
+ * reference camera's (+0.0 and 1.0) is no view: the frame runs exactly the code it runs without
+ * one.  Any other view is generated in the kernel from the launch's arguments (one basis per
+ * frame of a launch), and its launch runs without the sky table and what rides on it (sky
+ * spans, shadow occluder masks, floor class): those are proofs about the fixed basis, so an
+ * oriented triangle-free frame takes the general trace kernel (what TRT_SKY_TABLE=0 runs).
+ * Oriented frames share launches, up to TRT_MAX_VIEW_FRAMES frames each with its own view. */
+typedef struct trt_view { float right[3], up[3], back[3]; } trt_view; /* 36 B */
+#define TRT_MAX_VIEW_FRAMES 32u
+
+/* host only: right = normalize(cross(front, world_up)), up = cross(right, front),
+ * back = -normalize(front); the reference's front (0,0,-1), up (0,1,0) give the identity bytes.
+ * TRT_ERR_INVALID for a null, non-finite, zero or parallel input. */
+int trt_view_look(trt_view* out, const float front[3], const float world_up[3]);
+
+/* host only, no context: the width*height Ray records (dir = w of step 2, .w = 1, resultColor 0)
+ * a host would bind as binding 1 for this view at spp 1; v NULL = the reference camera. */
+int trt_view_rays(const trt_params* p, const trt_view* v, trt_ray* out);
+
+/* the context's view for trt_render, trt_render_frames and the multi-GPU calls;
+ * NULL restores the reference camera.  Copied.  TRT_ERR_INVALID if not finite (the view in
+ * force stays). */
+int trt_set_view(trt_ctx* ctx, const trt_view* v);
+
+/* trt_render_frames with one view per frame; views NULL = the context's view for every frame.
+ * Views do not split launches (only the TRT_MAX_VIEW_FRAMES clamp of a launch with an oriented
+ * frame does); a call whose views are all the reference camera enqueues what trt_render_frames
+ * enqueues.  TRT_ERR_INVALID if a view is not finite. */
+int trt_render_frames_view(trt_ctx* ctx, const trt_params* p, const trt_ubo* ubos, const trt_view* views,
+                           uint32_t nframes, uint8_t* out_rgba8, size_t frame_stride, uint32_t time_every);
+
 /* Device time per frame (ms) of each launch timed by the last timed trt_render_frames call:
  * the launch's event span divided by the frames it traced (waits for them); n <= the number
  * of timed launches, trt_timed_launches(). */
@@ -314,6 +357,9 @@ int trt_render_multi(trt_multi* m, const trt_params* p, uint32_t band_rows, int 
 int trt_render_multi_frames(trt_multi* m, const trt_params* p, const trt_ubo* ubos, uint32_t nframes,
                             uint32_t band_rows, int root, uint32_t frames_per_gather,
                             uint8_t* const* out_rgba8, size_t frame_stride);
+/* trt_set_view on every local context of m: trt_render_multi and trt_render_multi_frames use each
+ * context's view (per-frame views of the tiled loop are not offered). */
+int trt_multi_set_view(trt_multi* m, const trt_view* v);
 /* Waits for every context stream of this process. */
 int trt_multi_synchronize(trt_multi* m);
 /* Test / diagnostic: with on != 0 the root's own band groups also travel through the gather

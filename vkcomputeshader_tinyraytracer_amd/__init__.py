@@ -9,6 +9,7 @@ from .scene import (
     MODEL_INFOS,
     Scene,
     SceneBuilder,
+    camera_orbit,
     camera_path,
     config_c1,
     config_c2,
@@ -20,10 +21,14 @@ from .scene import (
     icosphere,
     make_ubo,
     synthetic_envmap,
+    view_look,
+    view_rays,
+    view_ypr,
 )
 
 __all__ = [
     "types", "ABI_SYMBOLS", "LIB_PATH", "TrtError", "lib", "Renderer", "render", "CONFIGS",
     "MODEL_INFOS", "Scene", "SceneBuilder", "camera_path", "config_c1", "config_c2", "config_c3", "config_c4",
     "config_c5", "config_readme", "config_reference_default", "icosphere", "make_ubo", "synthetic_envmap", "write_image",
+    "camera_orbit", "view_look", "view_rays", "view_ypr",
 ]

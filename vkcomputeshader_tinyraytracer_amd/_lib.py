@@ -77,6 +77,10 @@ def lib() -> ctypes.CDLL:
         "trt_set_deferred_shadows": (c_int, [vp, c_int]),
         "trt_defer_stats": (c_int, [vp, c_u32, ctypes.POINTER(ctypes.c_uint64)]),
         "trt_render_frames": (c_int, [vp, ctypes.POINTER(Params), vp, c_u32, vp, ctypes.c_size_t, c_u32]),
+        "trt_view_look": (c_int, [vp, f3, f3]),
+        "trt_view_rays": (c_int, [ctypes.POINTER(Params), vp, vp]),
+        "trt_set_view": (c_int, [vp, vp]),
+        "trt_render_frames_view": (c_int, [vp, ctypes.POINTER(Params), vp, vp, c_u32, vp, ctypes.c_size_t, c_u32]),
         "trt_frame_times": (c_int, [vp, ctypes.POINTER(ctypes.c_float), c_u32]),
         "trt_timed_launches": (c_u32, [vp, ctypes.POINTER(c_u32), c_u32]),
         "trt_set_frame_batch": (c_int, [vp, c_u32]),
@@ -119,6 +123,7 @@ def lib() -> ctypes.CDLL:
                                      ctypes.POINTER(Stats)]),
         "trt_render_multi_frames": (c_int, [vp, ctypes.POINTER(Params), vp, c_u32, c_u32, c_int, c_u32,
                                             ctypes.POINTER(vp), ctypes.c_size_t]),
+        "trt_multi_set_view": (c_int, [vp, vp]),
         "trt_multi_synchronize": (c_int, [vp]),
         "trt_multi_set_self_gather": (c_int, [vp, c_int]),
         "trt_frame_root": (c_u32, [c_u32, c_u32, c_int]),
@@ -137,6 +142,9 @@ def lib() -> ctypes.CDLL:
     return L
 
 
+# TRT_ABI_VERSION of include/trt/abi.h (trt_version() prints it).
+ABI_VERSION = 5
+
 # Every symbol include/trt/abi.h declares (checked by tests/test_abi.py).
 ABI_SYMBOLS = (
     "trt_version",
@@ -152,6 +160,10 @@ ABI_SYMBOLS = (
     "trt_set_deferred_shadows",
     "trt_defer_stats",
     "trt_render_frames",
+    "trt_view_look",
+    "trt_view_rays",
+    "trt_set_view",
+    "trt_render_frames_view",
     "trt_frame_times",
     "trt_timed_launches",
     "trt_set_frame_batch",
@@ -192,6 +204,7 @@ ABI_SYMBOLS = (
     "trt_multi_update_ubo",
     "trt_render_multi",
     "trt_render_multi_frames",
+    "trt_multi_set_view",
     "trt_multi_synchronize",
     "trt_multi_set_self_gather",
     "trt_frame_root",

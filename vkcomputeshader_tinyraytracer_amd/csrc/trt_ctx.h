@@ -28,6 +28,10 @@ struct trt_ctx {
     std::string err;
     trt_ubo ubo{};
     bool have_scene = false;
+    // The context's view (trt_set_view).  view_on: it is not the reference camera's bytes, so
+    // frames without a view of their own are oriented (KArgs::view_on).
+    trt_view view{{1.0f, 0.0f, 0.0f}, {0.0f, 1.0f, 0.0f}, {0.0f, 0.0f, 1.0f}};
+    bool view_on = false;
 
     trt::BatchRec* d_batches = nullptr;
     float4* d_nodes = nullptr; // implicit 8-ary hierarchy over the batches
@@ -165,15 +169,18 @@ namespace trt {
 hipError_t touch_stream(hipStream_t s, void* scratch);
 
 // One frame of a frame loop: its UBO (null: the context's current one), its RGBA8 image (a
-// device pointer, or null) and whether a band launch writes its rows at their frame rows.
+// device pointer, or null), whether a band launch writes its rows at their frame rows, and its
+// view (null: the context's).
 struct FrameOut {
     const trt_ubo* ubo;
     uint8_t* out8;
     bool in_place;
+    const trt_view* view = nullptr;
 };
 // The frame loop behind trt_render_frames and the multi-GPU band renders: plain frames go
-// out as multi-frame launches (up to kMaxLaunchFrames frames sharing everything but camPos and
-// the output), split / deferred-shadow frames one launch sequence per frame; launches rotate
+// out as multi-frame launches (up to kMaxLaunchFrames frames sharing everything but camPos, the
+// view and the output; a launch with an oriented frame up to kMaxViewFrames), split /
+// deferred-shadow frames one launch sequence per frame; launches rotate
 // over the frames-in-flight streams forked from and joined back into the context's stream.
 // Only enqueues.  time_every > 0: HIP events bracket every time_every-th launch.
 int render_frame_list(trt_ctx* c, const trt_params* p, const FrameOut* frames, uint32_t n, uint32_t time_every);

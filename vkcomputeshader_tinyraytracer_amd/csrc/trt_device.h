@@ -170,8 +170,11 @@ struct SphereArg {
 // one frame's slow tiles (the glass sphere) overlap the next frame's tiles inside one grid —
 // no stream switch, no launch gap, one drain per launch instead of per frame.  The frames of
 // a launch share every UBO field but the camera position (the reference's interactive loop
-// moves only camPos, main.cpp:391-403, 2165-2179) and each writes its own image.
+// moves only camPos, main.cpp:391-403, 2165-2179) and each writes its own image; each may also
+// have a view basis of its own (KArgs::view).
 constexpr uint32_t kMaxLaunchFrames = 64;
+// Frames of an oriented launch (KArgs::view, one basis per frame; abi.h TRT_MAX_VIEW_FRAMES)
+constexpr uint32_t kMaxViewFrames = 32;
 // Tile dealing of multi-frame launches (trt_kernel.hip xcd_tile, trt_ctx xcd_rot / xcd_skew)
 constexpr uint32_t kDefaultXcdRot = 1, kDefaultXcdSkew = 0, kDefaultXcdInter = 1;
 struct FrameRec {
@@ -264,7 +267,15 @@ struct KArgs {
     // 0xffff, word >> 16) outside which every tile is all sky in every frame of the table.
     // span_tables 0: none (always so when sky is null).
     uint32_t span_tables, span_shift, span_ntr;
-    uint32_t span[kSpanWords];
+    // View basis (abi.h trt_view; primary_dir): view_on != 0 marks an oriented launch, whose frame
+    // f generates its primary rays in the basis view[f] = right[3], up[3], back[3] (frames of the
+    // reference camera carry the identity basis, which reproduces their rays bit for bit).  An
+    // oriented launch has at most kMaxViewFrames frames and no sky table, hence no spans: the
+    // bases share the spans' bytes.  Wave-uniform, so a frame's basis is nine scalar loads.
+    union {
+        uint32_t span[kSpanWords];
+        float view[kMaxViewFrames][9];
+    };
     // Shadow occluder masks (shadow_mask.h; sky_trace_kernel_smask only), or null (every sphere is
     // tested): bit 4 * i + j of a mask = sphere j may occlude light i.  smask: smask_nx x smask_nz
     // floor cells, cell (int((x + 10) * smask_inv), int((z + 30) * smask_inv)) clamped; smask_rows:
@@ -277,7 +288,9 @@ struct KArgs {
     // holds floor_pack words, c0 | c1 << 8 | s0 << 16 | s1 << 24 — a tile inside [c0, c1) and
     // outside the sphere interval [s0, s1) can only hit the floor.  0: `span` as above.
     uint32_t floor_class;
+    uint32_t view_on;
 };
+static_assert(sizeof(float) * 9 * kMaxViewFrames <= sizeof(uint32_t) * kSpanWords, "the view bases fit the spans' bytes");
 static_assert(sizeof(KArgs) <= 4096, "KArgs fits the 4 KB kernel-argument limit");
 
 } // namespace trt

@@ -2143,7 +2143,15 @@ __device__ __forceinline__ uint32_t pcg_hash(uint32_t v) {
     return (word >> 22u) ^ word;
 }
 
-__device__ __forceinline__ f3 primary_dir(const KArgs& A, uint32_t x, uint32_t y, uint32_t sample) {
+// VIEW: frame f of an oriented launch (A.view_on; abi.h trt_view) turns the host direction into
+// its basis A.view[f] before the shader's normalize: w = (c.x * right + c.y * up) + c.z * back,
+// each product and sum rounded on its own (-ffp-contract=off), which is what a host would have
+// stored into binding 1 (trt_view_rays is the host twin).  f and the launch's view_on are
+// wave-uniform, so the basis is nine scalar loads from the kernel arguments and the step nine
+// VALU operations with scalar operands.  Replayed rays (rays_in) are the caller's and stay as
+// they are.  The sky table's kernels never see a view (VIEW false: attach_sky).
+template <bool VIEW = true>
+__device__ __forceinline__ f3 primary_dir(const KArgs& A, uint32_t x, uint32_t y, uint32_t sample, uint32_t f = 0) {
     const uint32_t W = A.width, H = A.height;
     const uint32_t pix = y * W + x; // W, H <= 65536: fits
     f3 d;
@@ -2169,6 +2177,11 @@ __device__ __forceinline__ f3 primary_dir(const KArgs& A, uint32_t x, uint32_t y
             dy = (float)H * 0.5f - ((float)row + jy);
         }
         d = normalize3(mk(dx, dy, A.dz)); // glm::normalize, main.cpp:1504
+        if (VIEW && A.view_on) {
+            const float* V = A.view[f]; // right[3], up[3], back[3]
+            d = mk((d.x * V[0] + d.y * V[3]) + d.z * V[6], (d.x * V[1] + d.y * V[4]) + d.z * V[7],
+                   (d.x * V[2] + d.y * V[5]) + d.z * V[8]);
+        }
     }
     return normalize3(d); // shader.comp:593
 }
@@ -2335,8 +2348,9 @@ __device__ __forceinline__ void floor_frame(const KArgs& A, const FrameRec& F, f
     store_pixel(A, F, o, mk(clamp01(c.x), clamp01(c.y), clamp01(c.z))); // cast_ray's clamp
 }
 
-// A floor-class tile in F0 and, for a frame pair, in F1: the primary direction (the camera only
-// translates, so it is the same in both frames) and the sky word once per wave.
+// A floor-class tile in F0 and, for a frame pair, in F1: the primary direction (frames with a
+// view never come here, so the camera only translates and it is the same in both frames) and the
+// sky word once per wave.
 __device__ __forceinline__ void floor_tile(const KArgs& A, uint32_t tile, const FrameRec& F0, const FrameRec* F1, Cnt& cnt,
                                            float4* slab) {
     const uint32_t lane = lane_id();
@@ -2344,7 +2358,7 @@ __device__ __forceinline__ void floor_tile(const KArgs& A, uint32_t tile, const 
     if (x >= A.width || k >= A.rows) return;
     const uint32_t y = band_row(A, k);
     const size_t o = (size_t)k * A.width + x;
-    const f3 d = primary_dir(A, x, y, 0);
+    const f3 d = primary_dir<false>(A, x, y, 0);
     const uint32_t word = A.sky[(size_t)y * A.width + x];
     floor_frame(A, F0, d, word, o, cnt, slab);
     if (F1) floor_frame(A, *F1, d, word, o, cnt, slab);
@@ -2379,7 +2393,7 @@ __device__ __forceinline__ void trace_tile(const KArgs& A, const FrameRec& F, ui
         L.stripe = ((tile * S + sub) * 0x9E3779B1u) >> (32 - 7);
         static_assert(kDeferStripes == 128u, "stripe hash yields 7 bits");
         const size_t o = valid ? (size_t)k * A.width + x : 0u;
-        const Seg root = valid ? Seg{orig, primary_dir(A, x, band_row(A, k), 0), 1.0f, 0} : Seg{orig, orig, 0.0f, 0};
+        const Seg root = valid ? Seg{orig, primary_dir(A, x, band_row(A, k), 0, frame), 1.0f, 0} : Seg{orig, orig, 0.0f, 0};
         defer_walk<GEOM, SPLIT>(A, lds, slab, L, valid, root, kEvRoot, (uint32_t)o);
         return;
     }
@@ -2392,7 +2406,7 @@ __device__ __forceinline__ void trace_tile(const KArgs& A, const FrameRec& F, ui
     const size_t o = (size_t)k * A.width + x;
     if (SPLIT) {
         bool spilled = false;
-        const f3 c = cast_seg<CAP, COUNT, GEOM, true>(A, Seg{orig, primary_dir(A, x, y, 0), 1.0f, 0}, cnt, lds,
+        const f3 c = cast_seg<CAP, COUNT, GEOM, true>(A, Seg{orig, primary_dir(A, x, y, 0, frame), 1.0f, 0}, cnt, lds,
                                                       slab, (uint32_t)o, spilled);
         cnt.pri += 1;
         const uint64_t sp = __ballot(spilled);
@@ -2415,13 +2429,13 @@ __device__ __forceinline__ void trace_tile(const KArgs& A, const FrameRec& F, ui
     if constexpr (SKY) {
         // Sky table (sky_trace_kernel: triangle-free spp-1 frames without rays_in / out32, A.sky
         // set): the primary rays are intersected here, and a wave whose rays all miss stores the
-        // words a primary miss of its pixels packs to (the camera only translates, so they are
-        // the same in every frame) and is done.  The load is issued before the tests and its
+        // words a primary miss of its pixels packs to (no frame of a launch with a table has a
+        // view, so its camera only translates and they are the same in every frame) and is done.  The load is issued before the tests and its
         // word is dead after the ballot; any other wave hands its root hits to cast_seg (ROOT),
         // and the missing lanes of a mixed tile take the per-ray background as before.
         static_assert(!SKY || (GEOM == 0 && !COUNT && !SPLIT && !DEFER), "the sky table serves plain GEOM 0 frames");
         {
-            const f3 d = primary_dir(A, x, y, 0);
+            const f3 d = primary_dir<false>(A, x, y, 0);
             const uint32_t word = A.sky[(size_t)y * A.width + x];
             Hit h;
             scene_intersect<false, 0>(A, orig, d, h, cnt, slab);
@@ -2439,7 +2453,7 @@ __device__ __forceinline__ void trace_tile(const KArgs& A, const FrameRec& F, ui
     const uint32_t spp = A.spp ? A.spp : 1u;
     f3 acc = mk(0.0f, 0.0f, 0.0f);
     for (uint32_t s = 0; s < spp; ++s) {
-        f3 d = primary_dir(A, x, y, s);
+        f3 d = primary_dir(A, x, y, s, frame);
         f3 c = cast_ray<CAP, COUNT, GEOM>(A, orig, d, cnt, lds, slab);
         acc = (spp == 1u) ? c : add(acc, c);
     }
@@ -2462,7 +2476,7 @@ __device__ __forceinline__ void trace_tile(const KArgs& A, const FrameRec& F, ui
 // with the same additions, and divided by spp — bit-identical to trace_tile's loop.
 template <int CAP, bool COUNT, int GEOM>
 __device__ __forceinline__ void trace_samples(const KArgs& A, const FrameRec& F, uint32_t tile, uint32_t sub, Cnt& cnt,
-                                              float* lds, float4* slab) {
+                                              float* lds, float4* slab, uint32_t frame) {
     const uint32_t lane = lane_id();
     if (tile >= A.ntiles) return;
     const uint32_t spp = A.spp, lg = 31u - __builtin_clz(64u / spp); // log2 of the pixels per wave
@@ -2475,7 +2489,7 @@ __device__ __forceinline__ void trace_samples(const KArgs& A, const FrameRec& F,
     f3 c = mk(0.0f, 0.0f, 0.0f);
     if (valid) {
         const f3 orig = mk(F.cam[0], F.cam[1], F.cam[2]);
-        c = cast_ray<CAP, COUNT, GEOM>(A, orig, primary_dir(A, x, band_row(A, k), smp), cnt, lds, slab);
+        c = cast_ray<CAP, COUNT, GEOM>(A, orig, primary_dir(A, x, band_row(A, k), smp, frame), cnt, lds, slab);
         cnt.pri += 1;
     }
     // the sample-order sum, gathered by every lane from its pixel's lanes (lane base + t holds
@@ -2553,7 +2567,7 @@ __device__ __forceinline__ uint32_t xcd_tile_base(const KArgs& A, uint32_t b) { 
 // F: the launch's frames (or frame pairs, frame_pair).
 // xcd_inter 2: no rotation — chunk group g's chunk on XCD x is the same in every frame of the
 // launch, so that XCD traces that chunk in all frames back to back and the texels its primary
-// rays miss into (the same directions in every frame: the camera only translates) stay in its L2;
+// rays miss into (the same directions in every frame while the camera only translates) stay in its L2;
 // the permuted classes (xcd_deal perm) keep the XCDs balanced without the rotation.
 __device__ __forceinline__ uint32_t inter_tile(const KArgs& A, uint32_t vb, uint32_t& f, uint32_t F) {
     const uint32_t tyn = A.ntiles / A.ntx;
@@ -2648,7 +2662,7 @@ __device__ __forceinline__ void trace_body(const KArgs& A) {
         const uint32_t per = A.ntiles * A.spp;
         f = vb / per;
         const uint32_t r = vb - f * per;
-        trace_samples<CAP, COUNT, GEOM>(A, A.fr[f], xcd_tile(A, r / A.spp), r % A.spp, cnt, lds, slab);
+        trace_samples<CAP, COUNT, GEOM>(A, A.fr[f], xcd_tile(A, r / A.spp), r % A.spp, cnt, lds, slab, f);
         if (COUNT) flush_counts(A, cnt);
         return;
     }
@@ -2687,8 +2701,9 @@ __device__ __forceinline__ void trace_body(const KArgs& A) {
                 }
             }
 #endif
-            trace_tile<CAP, COUNT, GEOM, SPLIT, DEFER, HYB, SKY, SMASK>(A, A.fr[f], tile, cnt, lds, slab);
-            if (f + 1u < A.nframes) trace_tile<CAP, COUNT, GEOM, SPLIT, DEFER, HYB, SKY, SMASK>(A, A.fr[f + 1u], tile, cnt, lds, slab);
+            trace_tile<CAP, COUNT, GEOM, SPLIT, DEFER, HYB, SKY, SMASK>(A, A.fr[f], tile, cnt, lds, slab, 0u, f);
+            if (f + 1u < A.nframes)
+                trace_tile<CAP, COUNT, GEOM, SPLIT, DEFER, HYB, SKY, SMASK>(A, A.fr[f + 1u], tile, cnt, lds, slab, 0u, f + 1u);
             if (COUNT) flush_counts(A, cnt);
             return;
         } else if (A.xcd_inter) {
@@ -2762,7 +2777,7 @@ __device__ __forceinline__ void trace_body(const KArgs& A) {
         }
     }
 #endif
-    trace_tile<CAP, COUNT, GEOM, SPLIT, DEFER, HYB, SKY, SMASK>(A, A.fr[f], tile, cnt, lds, slab);
+    trace_tile<CAP, COUNT, GEOM, SPLIT, DEFER, HYB, SKY, SMASK>(A, A.fr[f], tile, cnt, lds, slab, 0u, f);
 #ifdef TRT_DIAG_WAVE_CLOCK
     __syncthreads();
     // single-frame launches write the records to out32; multi-frame launches to the diagnostic
@@ -3036,7 +3051,7 @@ __global__ __launch_bounds__(64, waves_per_simd<GEOM>()) void defer_fallback(KAr
             if (i < n) {
                 const uint32_t o = S.fb[i];
                 const uint32_t k = o / A.width, x = o % A.width;
-                const f3 c = cast_ray<CAP, false, GEOM>(A, orig, primary_dir(A, x, band_row(A, k), 0), cnt, lds, slab);
+                const f3 c = cast_ray<CAP, false, GEOM>(A, orig, primary_dir(A, x, band_row(A, k), 0, f), cnt, lds, slab);
                 store_pixel(A, A.fr[f], o, c);
             }
         }
@@ -3252,8 +3267,9 @@ hipError_t launch_envp(const uint32_t* env, uint2* out, uint32_t W, uint32_t H, 
 // ---- sky table (KArgs::sky) ----------------------------------------------------------------
 //
 // Entry y * width + x is the RGBA8 word store_pixel writes for a primary ray of frame pixel
-// (x, y) that misses the scene: the ray's direction depends only on the pixel (the camera only
-// translates, main.cpp:391-403; the reference itself builds its directions once, :1496-1506), and
+// (x, y) that misses the scene: the ray's direction depends only on the pixel (without a view the
+// camera only translates, main.cpp:391-403, and the reference itself builds its directions once,
+// :1496-1506; a launch with a view gets no table, attach_sky), and
 // a miss's colour only on the direction and the envmap.  Built with the frame's own functions
 // (primary_dir, background, cast_seg's accumulation, cast_ray's clamp, gamma3, pack_rgba8), so
 // the words are the frame's bit for bit.  A: the frame's arguments with spp 1 and no rays_in.
@@ -3262,7 +3278,7 @@ namespace trt {
 __global__ __launch_bounds__(256) void sky_kernel(KArgs A, uint32_t* __restrict__ out) {
     const uint32_t x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y;
     if (x >= A.width || y >= A.height) return;
-    const f3 d = primary_dir(A, x, y, 0);
+    const f3 d = primary_dir<false>(A, x, y, 0);
     const f3 bg = background(A, d);
     const f3 c = add(mk(0.0f, 0.0f, 0.0f), muls(bg, 1.0f));
     out[(size_t)y * A.width + x] = pack_rgba8(A, gamma3(mk(clamp01(c.x), clamp01(c.y), clamp01(c.z))));

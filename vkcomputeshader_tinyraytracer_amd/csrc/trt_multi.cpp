@@ -629,6 +629,14 @@ int trt_multi_update_ubo(trt_multi* m, const trt_ubo* ubo) {
     return TRT_OK;
 }
 
+// The band renders below go through each context (trt_render, render_frame_list), so they use
+// its view.
+int trt_multi_set_view(trt_multi* m, const trt_view* v) {
+    if (!m) return TRT_ERR_INVALID;
+    for (auto& d : m->devs) MTRY(m, d.ctx, trt_set_view(d.ctx, v));
+    return TRT_OK;
+}
+
 int trt_render_multi(trt_multi* m, const trt_params* p, uint32_t band_rows, int root, uint8_t* const* out8,
                      trt_stats* st) {
     int rc = check_common(m, p, band_rows, root);

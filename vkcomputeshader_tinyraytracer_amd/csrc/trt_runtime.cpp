@@ -161,6 +161,22 @@ void fill_frame(trt::FrameRec& f, const trt_ubo& u, uint8_t* out8, bool in_place
     f.out8 = reinterpret_cast<uint32_t*>(out8);
 }
 
+// Views (abi.h trt_view).  The reference camera's 36 bytes are "no view": such a frame is not
+// oriented and runs what it ran before there were views.
+const trt_view kViewIdentity{{1.0f, 0.0f, 0.0f}, {0.0f, 1.0f, 0.0f}, {0.0f, 0.0f, 1.0f}};
+bool view_is_identity(const trt_view& v) { return std::memcmp(&v, &kViewIdentity, sizeof(trt_view)) == 0; }
+bool view_is_finite(const trt_view& v) {
+    const float* f = v.right; // right, up, back: nine consecutive floats
+    for (int i = 0; i < 9; ++i)
+        if (!std::isfinite(f[i])) return false;
+    return true;
+}
+// Frame f's basis of an oriented launch (KArgs::view): right[3], up[3], back[3].
+void fill_view(KArgs& A, uint32_t f, const trt_view& v) {
+    static_assert(sizeof(trt_view) == sizeof(A.view[0]), "a view is nine floats");
+    std::memcpy(A.view[f], &v, sizeof(trt_view));
+}
+
 // Frames that may share a launch: every UBO field but camPos equal (byte-wise).
 bool same_but_camera(const trt_ubo& a, const trt_ubo& b) {
     constexpr size_t cam = offsetof(trt_ubo, camPos);
@@ -174,7 +190,67 @@ bool same_but_camera(const trt_ubo& a, const trt_ubo& b) {
 
 extern "C" {
 
-const char* trt_version(void) { return "trt-mi355x 0.2 (gfx950, abi 2)"; }
+#define TRT_STR2(x) #x
+#define TRT_STR(x) TRT_STR2(x)
+const char* trt_version(void) { return "trt-mi355x 0.2 (gfx950, abi " TRT_STR(TRT_ABI_VERSION) ")"; }
+
+int trt_set_view(trt_ctx* c, const trt_view* v) {
+    if (!c) return TRT_ERR_INVALID;
+    if (v && !view_is_finite(*v)) return fail(c, TRT_ERR_INVALID, "trt_set_view: the view is not finite");
+    c->view = v ? *v : kViewIdentity;
+    c->view_on = !view_is_identity(c->view);
+    return TRT_OK;
+}
+
+int trt_view_look(trt_view* out, const float front[3], const float world_up[3]) {
+    if (!out || !front || !world_up) return TRT_ERR_INVALID;
+    for (int a = 0; a < 3; ++a)
+        if (!std::isfinite(front[a]) || !std::isfinite(world_up[a])) return TRT_ERR_INVALID;
+    const float fl = std::sqrt((front[0] * front[0] + front[1] * front[1]) + front[2] * front[2]);
+    if (!(fl > 0.0f) || !std::isfinite(fl)) return TRT_ERR_INVALID;
+    const float f[3] = {front[0] / fl, front[1] / fl, front[2] / fl};
+    // cross(front, up): the right vector processInput walks along (main.cpp:391-403)
+    float r[3] = {f[1] * world_up[2] - world_up[1] * f[2], f[2] * world_up[0] - world_up[2] * f[0],
+                  f[0] * world_up[1] - world_up[0] * f[1]};
+    const float rl = std::sqrt((r[0] * r[0] + r[1] * r[1]) + r[2] * r[2]);
+    const float ul = std::sqrt((world_up[0] * world_up[0] + world_up[1] * world_up[1]) + world_up[2] * world_up[2]);
+    if (!std::isfinite(rl) || !std::isfinite(ul) || !(rl > 1e-6f * ul)) return TRT_ERR_INVALID; // zero up, or front || up
+    for (int a = 0; a < 3; ++a) r[a] = r[a] / rl;
+    const float u[3] = {r[1] * f[2] - f[1] * r[2], r[2] * f[0] - f[2] * r[0], r[0] * f[1] - f[0] * r[1]};
+    for (int a = 0; a < 3; ++a) {
+        out->right[a] = r[a] + 0.0f; // -0.0 -> +0.0: the reference's vectors give the identity bytes
+        out->up[a] = u[a] + 0.0f;
+        out->back[a] = -f[a] + 0.0f;
+    }
+    return TRT_OK;
+}
+
+int trt_view_rays(const trt_params* p, const trt_view* v, trt_ray* out) {
+    if (!p || !out || p->width == 0 || p->height == 0 || p->width > 65536 || p->height > 65536) return TRT_ERR_INVALID;
+    const trt_view& V = v ? *v : kViewIdentity;
+    const uint32_t W = p->width, H = p->height;
+    // dir_z as fill_args (main.cpp:1503); the rest is primary_dir's spp-1 arithmetic, operation
+    // for operation (this file compiles with -ffp-contract=off)
+    const float dz = (float)(-1.0 * ((double)H / (2.0 * std::tan((double)p->fov / 2.0))));
+    for (uint32_t y = 0; y < H; ++y) {
+        for (uint32_t x = 0; x < W; ++x) {
+            const uint32_t row = ((p->flags & TRT_FLAG_ROW_QUIRK) && x + 1u == W) ? y + 1u : y;
+            const float dx = ((float)x + 0.5f) - (float)W * 0.5f;
+            const float dy = -((float)row + 0.5f) + (float)H * 0.5f;
+            const float inv = 1.0f / std::sqrt((dx * dx + dy * dy) + dz * dz);
+            const float cx = dx * inv, cy = dy * inv, cz = dz * inv;
+            trt_ray& r = out[(size_t)y * W + x];
+            std::memset(&r, 0, sizeof(r));
+            float w[3];
+            for (int a = 0; a < 3; ++a) w[a] = (cx * V.right[a] + cy * V.up[a]) + cz * V.back[a];
+            r.dir.x = w[0];
+            r.dir.y = w[1];
+            r.dir.z = w[2];
+            r.dir.w = 1.0f;
+        }
+    }
+    return TRT_OK;
+}
 
 void trt_params_default(trt_params* p) {
     if (!p) return;
@@ -605,6 +681,9 @@ int ensure_envp(trt_ctx* c, const trt_params* p, hipStream_t stream) {
 int attach_sky(trt_ctx* c, KArgs& A, bool count, hipStream_t stream) {
     A.sky = nullptr;
     if (!c->sky_on || c->nbatch != 0 || A.spp > 1 || A.rays_in || A.out32 || count) return TRT_OK;
+    // an oriented launch: the table (and the spans, masks and floor class, which all need it)
+    // holds the fixed basis's primary misses
+    if (A.view_on) return TRT_OK;
     if ((A.flags & TRT_FLAG_ENVMAP) && !c->d_env) return TRT_OK;
     const uint32_t kflags = A.flags & (TRT_FLAG_ROW_QUIRK | TRT_FLAG_SRGB_OUT | TRT_FLAG_ENVMAP);
     const trt_ctx::SkyKey key{A.width, A.height, kflags, A.dz, (A.flags & TRT_FLAG_ENVMAP) ? c->env_gen : 0u};
@@ -791,6 +870,9 @@ void fill_args(trt_ctx* c, const trt_params* p, KArgs& A) {
     fill_ubo_args(A, c->ubo);
     A.nframes = 1;
     fill_frame(A.fr[0], c->ubo, nullptr, (p->flags & TRT_FLAG_BAND_IN_PLACE) != 0);
+    // the context's view (trt_set_view); replayed rays are the caller's directions and win
+    A.view_on = (c->view_on && !p->rays_in) ? 1u : 0u;
+    if (A.view_on) fill_view(A, 0, c->view);
     A.batches = c->d_batches;
     A.geo = c->d_geo;
     A.shade = c->d_shade;
@@ -1158,7 +1240,23 @@ int render_frame_list(trt_ctx* c, const trt_params* p, const FrameOut* frames, u
     KArgs A;
     fill_args(c, p, A);
     A.rays_in = reinterpret_cast<const float*>(p->rays_in);
+    // a frame's view: its own, else the context's; null for the reference camera's bytes and
+    // under replayed rays (such a frame is not oriented)
+    auto view_of = [&](uint32_t i) -> const trt_view* {
+        if (p->rays_in) return nullptr;
+        const trt_view* v = frames[i].view ? frames[i].view : (c->view_on ? &c->view : nullptr);
+        return (v && !view_is_identity(*v)) ? v : nullptr;
+    };
+    bool any_plain_view = false;
+    for (uint32_t i = 0; i < nframes; ++i) {
+        if (frames[i].view && !view_is_finite(*frames[i].view))
+            return fail(c, TRT_ERR_INVALID, "trt_render_frames_view: a view is not finite");
+        if (!view_of(i)) any_plain_view = true;
+    }
+    // the sky table serves the launches without an oriented frame (set per launch below)
+    A.view_on = any_plain_view ? 0u : 1u;
     if (A.rows != 0 && nframes != 0 && (rc = attach_sky(c, A, false, c->stream)) != TRT_OK) return rc;
+    const uint32_t* const sky = A.sky;
     auto ubo_of = [&](uint32_t i) -> const trt_ubo& { return frames[i].ubo ? *frames[i].ubo : c->ubo; };
     if (A.rows == 0 || nframes == 0) {
         if (nframes) c->ubo = ubo_of(nframes - 1);
@@ -1194,10 +1292,22 @@ int render_frame_list(trt_ctx* c, const trt_params* p, const FrameOut* frames, u
     if (!c->frames_in_flight && defer) want = fit_defer_slots(c, p, want, group);
     const uint32_t cap = plain ? (c->frame_batch ? c->frame_batch : trt::kMaxLaunchFrames) : group;
     const uint32_t per_launch = std::max(1u, std::min(cap, (nframes + want - 1) / want));
-    // launches: runs of consecutive frames sharing every UBO field but camPos
+    // launches: runs of consecutive frames sharing every UBO field but camPos.  Views do not
+    // split launches; a launch with an oriented frame holds at most kMaxViewFrames frames (one
+    // basis each in KArgs::view), so a run breaks where it would outgrow that
     std::vector<uint32_t> first{0};
-    for (uint32_t i = 1; i < nframes; ++i)
-        if (i - first.back() >= per_launch || !same_but_camera(ubo_of(i), ubo_of(first.back()))) first.push_back(i);
+    bool run_oriented = view_of(0) != nullptr;
+    for (uint32_t i = 1; i < nframes; ++i) {
+        const bool o = view_of(i) != nullptr;
+        const uint32_t len = i - first.back();
+        if (len >= per_launch || !same_but_camera(ubo_of(i), ubo_of(first.back())) ||
+            ((run_oriented || o) && len >= trt::kMaxViewFrames)) {
+            first.push_back(i);
+            run_oriented = o;
+        } else {
+            run_oriented = run_oriented || o;
+        }
+    }
     const uint32_t nl = (uint32_t)first.size();
     first.push_back(nframes);
     if (timing) {
@@ -1237,9 +1347,22 @@ int render_frame_list(trt_ctx* c, const trt_params* p, const FrameOut* frames, u
         fill_ubo_args(A, c->ubo);
         A.nframes = n;
         for (uint32_t k = 0; k < n; ++k) fill_frame(A.fr[k], ubo_of(i0 + k), frames[i0 + k].out8, frames[i0 + k].in_place);
+        // an oriented launch: no sky table (so no spans, masks or floor class below), and every
+        // frame's basis, the identity for its frames of the reference camera
+        A.view_on = 0;
+        for (uint32_t k = 0; k < n; ++k)
+            if (view_of(i0 + k)) A.view_on = 1;
+        A.sky = A.view_on ? nullptr : sky;
         fill_spans(c, A);
         if ((rc = attach_smask(c, A, c->stream)) != TRT_OK) return rc;
         attach_floor_class(c, A);
+        if (A.view_on) { // after the span words: the bases share their bytes (none here: no table)
+            if (n > trt::kMaxViewFrames) return fail(c, TRT_ERR_INVALID, "trt_render_frames: oriented launch too long");
+            for (uint32_t k = 0; k < n; ++k) {
+                const trt_view* v = view_of(i0 + k);
+                fill_view(A, k, v ? *v : kViewIdentity);
+            }
+        }
         uint32_t slot = j % nfl;
         if ((rc = prepare_split(c, p, A, slot, sv[slot])) != TRT_OK) {
             // auto count: a slot whose scratch does not fit in device memory is dropped, with the
@@ -1275,16 +1398,22 @@ int render_frame_list(trt_ctx* c, const trt_params* p, const FrameOut* frames, u
 
 } // namespace trt
 
-extern "C" int trt_render_frames(trt_ctx* c, const trt_params* p, const trt_ubo* ubos, uint32_t nframes,
-                                 uint8_t* out8, size_t frame_stride, uint32_t time_every) {
+extern "C" int trt_render_frames_view(trt_ctx* c, const trt_params* p, const trt_ubo* ubos, const trt_view* views,
+                                      uint32_t nframes, uint8_t* out8, size_t frame_stride, uint32_t time_every) {
     if (!c) return TRT_ERR_INVALID;
     if (!p) return fail(c, TRT_ERR_INVALID, "trt_render_frames: null params");
     std::vector<trt::FrameOut> fl(nframes);
     const bool in_place = (p->flags & TRT_FLAG_BAND_IN_PLACE) != 0;
     for (uint32_t i = 0; i < nframes; ++i)
-        fl[i] = trt::FrameOut{ubos ? &ubos[i] : nullptr, out8 ? out8 + (size_t)i * frame_stride : nullptr, in_place};
+        fl[i] = trt::FrameOut{ubos ? &ubos[i] : nullptr, out8 ? out8 + (size_t)i * frame_stride : nullptr, in_place,
+                              views ? &views[i] : nullptr};
     // TRT_FLAG_TIMING: events around every time_every-th launch (0 or 1: every launch)
     return trt::render_frame_list(c, p, fl.data(), nframes, (p->flags & TRT_FLAG_TIMING) ? std::max(time_every, 1u) : 0u);
+}
+
+extern "C" int trt_render_frames(trt_ctx* c, const trt_params* p, const trt_ubo* ubos, uint32_t nframes,
+                                 uint8_t* out8, size_t frame_stride, uint32_t time_every) {
+    return trt_render_frames_view(c, p, ubos, nullptr, nframes, out8, frame_stride, time_every);
 }
 
 extern "C" int trt_set_frame_batch(trt_ctx* c, uint32_t n) {

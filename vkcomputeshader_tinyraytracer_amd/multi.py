@@ -131,6 +131,12 @@ class MultiRenderer:
         u = np.ascontiguousarray(ubo)
         self._check(self._L.trt_multi_update_ubo(self._h, u.ctypes.data))
 
+    def set_view(self, view) -> None:
+        """trt_multi_set_view: the view (a T.VIEW record, or None = the reference camera) of every
+        local context; draw_frame and render_frames trace every band in it."""
+        v = None if view is None else np.ascontiguousarray(view, T.VIEW)
+        self._check(self._L.trt_multi_set_view(self._h, None if v is None else v.ctypes.data))
+
     def _outs(self, outs, need: int, device: bool):
         """The C array of output pointers, after checking every given output: contiguous uint8
         of >= `need` bytes, on the device (torch CUDA) or the host (numpy) as the call needs."""

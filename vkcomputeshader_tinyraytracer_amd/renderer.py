@@ -56,6 +56,25 @@ class Renderer:
         u = np.ascontiguousarray(ubo)
         self._check(self._L.trt_update_ubo(self._h, u.ctypes.data))
 
+    def set_view(self, view) -> None:
+        """The context's view (trt_set_view): a T.VIEW record (scene.view_look / view_ypr), or None
+        for the reference camera.  Every later draw_frame and every render_frames frame without
+        a view of its own is generated in this basis; rays_in, where given, wins."""
+        if view is None:
+            self._check(self._L.trt_set_view(self._h, None))
+            return
+        v = np.ascontiguousarray(view, T.VIEW)
+        self._check(self._L.trt_set_view(self._h, v.ctypes.data))
+
+    @staticmethod
+    def _views(views, nframes: int):
+        if views is None:
+            return None
+        v = np.ascontiguousarray(views, T.VIEW).reshape(-1)
+        if v.shape[0] < nframes:
+            raise ValueError(f"{v.shape[0]} views for {nframes} frames")
+        return v
+
     def set_frames_in_flight(self, n: int) -> None:
         """Frames of render_frames that may run concurrently (trt_set_frames_in_flight; the
         reference's MAX_FRAMES_IN_FLIGHT = 2, main.cpp:45): 1..32, or 0 = auto (4; 16 for
@@ -148,10 +167,11 @@ class Renderer:
         return out8, out32, st.as_dict()
 
     def render_frames(self, params: T.Params, out8, nframes: int, ubos: np.ndarray | None = None,
-                      frame_stride: int = 0, timing: bool = False, time_every: int = 1) -> int:
+                      frame_stride: int = 0, timing: bool = False, time_every: int = 1, views=None) -> int:
         """Native frame loop (trt_render_frames): `nframes` frames enqueued on the context's
         stream into the device tensor `out8` (+ i * frame_stride bytes); plain frames go out
-        several per launch (set_frame_batch).
+        several per launch (set_frame_batch).  `views`: one T.VIEW per frame
+        (trt_render_frames_view; scene.camera_orbit), or None = the context's view for all.
 
         With `timing`, launches 0, time_every, 2*time_every, ... are bracketed by HIP events;
         returns how many were (read them with frame_times / launch_frames)."""
@@ -173,12 +193,18 @@ class Renderer:
             u = np.ascontiguousarray(ubos, T.UBO)
             if u.shape[0] < nframes:
                 raise ValueError(f"{u.shape[0]} UBOs for {nframes} frames")
-        self._check(self._L.trt_render_frames(self._h, ctypes.byref(p), u.ctypes.data if u is not None else None,
-                                              nframes, out8.data_ptr(), frame_stride, time_every))
+        v = self._views(views, nframes)
+        up = u.ctypes.data if u is not None else None
+        if v is None:
+            self._check(self._L.trt_render_frames(self._h, ctypes.byref(p), up, nframes, out8.data_ptr(),
+                                                  frame_stride, time_every))
+        else:
+            self._check(self._L.trt_render_frames_view(self._h, ctypes.byref(p), up, v.ctypes.data, nframes,
+                                                       out8.data_ptr(), frame_stride, time_every))
         return int(self._L.trt_timed_launches(self._h, None, 0)) if timing else 0
 
     def frames_call(self, params: T.Params, out8, nframes: int, ubos: np.ndarray | None = None,
-                    frame_stride: int = 0):
+                    frame_stride: int = 0, views=None):
         """render_frames(params, out8, nframes, ubos, frame_stride) with its argument checks and
         conversions done once: returns a zero-argument callable that only enqueues the frames
         (one trt_render_frames call), for host loops that re-issue the same frame list."""
@@ -198,7 +224,18 @@ class Renderer:
                 raise ValueError(f"{u.shape[0]} UBOs for {nframes} frames")
         fn, h, pp = self._L.trt_render_frames, self._h, ctypes.byref(p)
         up, op = (u.ctypes.data if u is not None else None), out8.data_ptr()
-        keep = (p, u, out8)  # alive as long as the callable
+        v = self._views(views, nframes)
+        keep = (p, u, out8, v)  # alive as long as the callable
+
+        if v is not None:  # one view per frame (trt_render_frames_view)
+            fnv, vp = self._L.trt_render_frames_view, v.ctypes.data
+
+            def call() -> None:
+                rc = fnv(h, pp, up, vp, nframes, op, frame_stride, 0)
+                if rc:
+                    self._check(rc)
+            call.keep = keep
+            return call
 
         def call() -> None:
             rc = fn(h, pp, up, nframes, op, frame_stride, 0)

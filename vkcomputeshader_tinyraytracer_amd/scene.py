@@ -113,6 +113,63 @@ def camera_path(ubo: np.ndarray, n: int, speed: float = 0.02) -> np.ndarray:
     return out
 
 
+# ---- views (abi.h trt_view) --------------------------------------------------------------
+
+VIEW_IDENTITY = np.zeros((), T.VIEW)
+VIEW_IDENTITY["right"], VIEW_IDENTITY["up"], VIEW_IDENTITY["back"] = (1, 0, 0), (0, 1, 0), (0, 0, 1)
+
+
+def _f3(v) -> ctypes.Array:
+    return (ctypes.c_float * 3)(*[float(np.float32(x)) for x in v])
+
+
+def view_look(front, up=(0.0, 1.0, 0.0)) -> np.ndarray:
+    """The view of a camera looking along `front` (trt_view_look): the reference's cameraFront
+    (0, 0, -1) and cameraUp (0, 1, 0) (main.cpp:342-344) give the reference camera's bytes."""
+    v = np.zeros((), T.VIEW)
+    rc = lib().trt_view_look(v.ctypes.data, _f3(front), _f3(up))
+    if rc != 0:
+        raise TrtError(rc, f"trt_view_look(front={tuple(front)}, up={tuple(up)}): zero, parallel or non-finite input")
+    return v
+
+
+def view_ypr(yaw: float, pitch: float, roll: float = 0.0) -> np.ndarray:
+    """The view M = Ry(yaw) Rx(pitch) Rz(roll), angles in degrees: computed in double, rounded
+    to float32; its columns are right, up, back.  (0, 0, 0) is the reference camera's bytes."""
+    y, p, r = (np.deg2rad(np.float64(a)) for a in (yaw, pitch, roll))
+    ry = np.array([[np.cos(y), 0, np.sin(y)], [0, 1, 0], [-np.sin(y), 0, np.cos(y)]], np.float64)
+    rx = np.array([[1, 0, 0], [0, np.cos(p), -np.sin(p)], [0, np.sin(p), np.cos(p)]], np.float64)
+    rz = np.array([[np.cos(r), -np.sin(r), 0], [np.sin(r), np.cos(r), 0], [0, 0, 1]], np.float64)
+    m = ((ry @ rx @ rz) + 0.0).astype(np.float32)  # + 0.0: no negative zeros
+    v = np.zeros((), T.VIEW)
+    v["right"], v["up"], v["back"] = m[:, 0], m[:, 1], m[:, 2]
+    return v
+
+
+def view_rays(params: T.Params, view=None) -> np.ndarray:
+    """The (height, width) Ray records a host would bind as binding 1 for `view` at spp 1
+    (trt_view_rays; None = the reference camera): the bit-exact host twin of the kernel's view
+    arithmetic, for replay through rays_in (draw_frame, the CPU oracle)."""
+    p = T.Params.from_buffer_copy(params)
+    out = np.zeros((p.height, p.width), T.RAY)
+    v = None if view is None else np.ascontiguousarray(view, T.VIEW)
+    rc = lib().trt_view_rays(ctypes.byref(p), None if v is None else v.ctypes.data, out.ctypes.data)
+    if rc != 0:
+        raise TrtError(rc, "trt_view_rays: bad image size")
+    return out
+
+
+def camera_orbit(ubo: np.ndarray, n: int, speed: float = 0.02, yaw_step: float = 1.0, pitch_step: float = -0.25,
+                 yaw0: float = 0.0, pitch0: float = 0.0) -> tuple[np.ndarray, np.ndarray]:
+    """camera_path with a camera that turns while it walks (mouse look held with W and D): n
+    per-frame UBOs and n views, frame k looking along view_ypr(yaw0 + k * yaw_step, pitch0 + k *
+    pitch_step).  For render_frames(..., ubos=, views=)."""
+    views = np.zeros(n, T.VIEW)
+    for k in range(n):
+        views[k] = view_ypr(yaw0 + k * yaw_step, pitch0 + k * pitch_step, 0.0)
+    return camera_path(ubo, n, speed), views
+
+
 # ---- synthetic inputs --------------------------------------------------------------------
 
 

@@ -43,7 +43,11 @@ UBO = np.dtype(
     ]
 )
 RAY = np.dtype([("dir", *F4), ("resultColor", *F4)])
+# trt_view (abi.h): the columns of the camera-to-world rotation, back = -front
+VIEW = np.dtype([("right", "<f4", (3,)), ("up", "<f4", (3,)), ("back", "<f4", (3,))])
+MAX_VIEW_FRAMES = 32  # TRT_MAX_VIEW_FRAMES: frames of a launch with an oriented frame
 
+assert VIEW.itemsize == 36
 assert MATERIAL.itemsize == 48 and SPHERE.itemsize == 64
 assert TRIANGLE.itemsize == 144 and MODEL.itemsize == 96
 assert UBO.itemsize == 352 and RAY.itemsize == 32
