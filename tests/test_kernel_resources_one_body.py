@@ -1,0 +1,54 @@
+"""Register, scratch and code-size budgets of the four sky kernels, read from the built gfx950
+code object (tools/kres.py, no GPU needed).  With one call site per body (sky_tile twice per
+pair, floor_frame in a rolled loop, no trace_samples) the kernels must stay at 5
+waves per SIMD (<= 96 VGPRs: 512 / 96 = 5) without scratch for CAP <= 4, and
+sky_trace_kernel_floor<3>, the kernel of the C2 headline, within 65,536 bytes of code (the parent
+commit's build: 126,732; this build: 59,980).  A frame pointer carried across trace_body's
+branches instead of a frame count puts the by-value KArgs copy into scratch (4 KB): the scratch
+assertion is what catches that.  Sizes and resource notes only: no instruction is read."""
+from __future__ import annotations
+
+import re
+import subprocess
+import sys
+from pathlib import Path
+
+import pytest
+
+REPO = Path(__file__).resolve().parents[1]
+OBJ = REPO / "build" / "csrc" / "trt_kernel.o"
+KERNELS = ("sky_trace_kernel_floor", "sky_trace_kernel_smask", "sky_trace_kernel", "sky_trace_kernel_nospan")
+CAPS = (0, 1, 2, 3, 4)
+VGPRS_PER_SIMD_LANE = 512  # gfx950: 512 VGPRs per lane of a SIMD, allocated in blocks of 8
+
+
+@pytest.fixture(scope="module")
+def resources():
+    # a missing object is a failed or skipped kernel build, not a missing GPU: fail, do not skip
+    assert OBJ.exists(), "build/csrc/trt_kernel.o is missing: run __graft_entry__.build() first"
+    out = subprocess.run([sys.executable, str(REPO / "tools" / "kres.py"), "sky_trace_kernel"], check=True,
+                         capture_output=True, text=True).stdout
+    res = {}
+    for line in out.splitlines():
+        m = re.match(r"(?:void )?trt::(\w+)<(\d+)>\(.*?\)\s+vgpr\s+(\d+)\s+sgpr\s+(\d+)\s+scratch\s+(\d+)\s+lds\s+(\d+)"
+                     r"\s+spill_v\s+(\d+)\s+code\s+(\d+)", line)
+        if m:
+            res[(m.group(1), int(m.group(2)))] = dict(vgpr=int(m.group(3)), sgpr=int(m.group(4)), scratch=int(m.group(5)),
+                                                      lds=int(m.group(6)), spill=int(m.group(7)), code=int(m.group(8)))
+    assert res, out[:500]
+    return res
+
+
+@pytest.mark.parametrize("kernel", KERNELS)
+@pytest.mark.parametrize("cap", CAPS)
+def test_sky_kernel_budget(resources, kernel, cap):
+    r = resources[(kernel, cap)]
+    assert r["vgpr"] <= 96, r
+    assert r["scratch"] == 0 and r["spill"] == 0, r
+    alloc = -(-r["vgpr"] // 8) * 8
+    assert min(8, VGPRS_PER_SIMD_LANE // alloc) == 5, r  # occupancy: the launch bound asks for 5 waves per SIMD
+
+
+def test_headline_kernel_fits_the_instruction_cache(resources):
+    r = resources[("sky_trace_kernel_floor", 3)]
+    assert 0 < r["code"] <= 65536, r

@@ -2,9 +2,10 @@
 """Per-kernel PMC summary of rocprofv3 --pmc passes (tools/r06.sh stage `pmc`): every counter
 summed over a kernel's dispatches, per wave, and the derived rates — VALU lanes per instruction
 (SQ_THREAD_CYCLES_VALU / SQ_ACTIVE_INST_VALU), the share of wave cycles waiting (SQ_WAIT_INST_ANY
-/ SQ_WAVE_CYCLES) and issuing VALU (SQ_ACTIVE_INST_VALU / SQ_WAVE_CYCLES), and TA / TD busy per
+/ SQ_WAVE_CYCLES) and issuing VALU (SQ_ACTIVE_INST_VALU / SQ_WAVE_CYCLES), TA / TD busy per
 unit (the *_BUSY_sum counters over the 256 CUs and GRBM_GUI_ACTIVE / 8: that counter is summed over
-the 8 XCDs, checked against the dispatch durations).  rocprofv3 serialises the
+the 8 XCDs, checked against the dispatch durations), and the instruction cache's requests and
+misses per wave with its miss ratio (SQC_ICACHE_*, SQ_IFETCH*).  rocprofv3 serialises the
 dispatches it counts, so these describe each kernel running alone.
 
   python tools/pmc_kernels.py gpurun_out/r06h/pmc [regex]   -> one JSON line per kernel
@@ -65,6 +66,13 @@ def main():
             if k in c and g:
                 div = g / NXCD * (NCU if k.endswith("_sum") else 1)
                 out[k.lower() + "_frac"] = round(c[k] / div, 3)
+        # instruction cache (SQC_ICACHE_*: per SQ and bank, summed) and instruction fetch, per wave
+        for k in sorted(c):
+            if "ICACHE" in k or "IFETCH" in k:
+                out[k.lower() + "_per_wave"] = round(c[k] / waves, 1)
+        if c.get("SQC_ICACHE_REQ"):
+            out["icache_miss_ratio"] = round(c.get("SQC_ICACHE_MISSES", 0.0) / c["SQC_ICACHE_REQ"], 4)
+            out["icache_miss_dup_ratio"] = round(c.get("SQC_ICACHE_MISSES_DUPLICATE", 0.0) / c["SQC_ICACHE_REQ"], 4)
         for k in ("FETCH_SIZE", "WRITE_SIZE", "TCC_HIT_sum", "TCC_MISS_sum"):
             if k in c:
                 out[k.lower()] = c[k]

@@ -2348,11 +2348,12 @@ __device__ __forceinline__ void floor_frame(const KArgs& A, const FrameRec& F, f
     store_pixel(A, F, o, mk(clamp01(c.x), clamp01(c.y), clamp01(c.z))); // cast_ray's clamp
 }
 
-// A floor-class tile in F0 and, for a frame pair, in F1: the primary direction (frames with a
-// view never come here, so the camera only translates and it is the same in both frames) and the
-// sky word once per wave.
-__device__ __forceinline__ void floor_tile(const KArgs& A, uint32_t tile, const FrameRec& F0, const FrameRec* F1, Cnt& cnt,
-                                           float4* slab) {
+// A floor-class tile in frames f .. f + nf - 1 of the launch (nf = 2 for a frame pair, else 1): the
+// primary direction (frames with a view never come here, so the camera only translates and it is
+// the same in both frames) and the sky word once per wave.  One floor_frame body in a rolled loop:
+// the body is short and far from the register cap, so what the loop hoists costs nothing, and the
+// second copy was 11 KB of the kernel's code.
+__device__ __forceinline__ void floor_tile(const KArgs& A, uint32_t tile, uint32_t f, uint32_t nf, Cnt& cnt, float4* slab) {
     const uint32_t lane = lane_id();
     const uint32_t x = (tile % A.ntx) * 8u + (lane & 7u), k = (tile / A.ntx) * 8u + (lane >> 3);
     if (x >= A.width || k >= A.rows) return;
@@ -2360,8 +2361,8 @@ __device__ __forceinline__ void floor_tile(const KArgs& A, uint32_t tile, const 
     const size_t o = (size_t)k * A.width + x;
     const f3 d = primary_dir<false>(A, x, y, 0);
     const uint32_t word = A.sky[(size_t)y * A.width + x];
-    floor_frame(A, F0, d, word, o, cnt, slab);
-    if (F1) floor_frame(A, *F1, d, word, o, cnt, slab);
+#pragma nounroll
+    for (uint32_t j = 0; j < nf; ++j) floor_frame(A, A.fr[f + j], d, word, o, cnt, slab);
 }
 
 // One 8x8 pixel tile of compact output rows: the wave's 64 lanes, one pixel each.  SPLIT
@@ -2372,8 +2373,7 @@ __device__ __forceinline__ void floor_tile(const KArgs& A, uint32_t tile, const 
 // its other lanes take work from the wave's segment pool as the trees grow, so a glass tile's
 // segments are spread over more waves (a shorter frame latency) at the price of idle lanes in
 // cheap tiles.
-template <int CAP, bool COUNT, int GEOM, bool SPLIT, bool DEFER = false, bool HYB = SPLIT, bool SKY = false,
-          bool SMASK = false>
+template <int CAP, bool COUNT, int GEOM, bool SPLIT, bool DEFER = false, bool HYB = SPLIT>
 __device__ __forceinline__ void trace_tile(const KArgs& A, const FrameRec& F, uint32_t tile, Cnt& cnt, float* lds,
                                            float4* slab, uint32_t sub = 0, uint32_t frame = 0) {
     const uint32_t lane = lane_id();
@@ -2426,30 +2426,6 @@ __device__ __forceinline__ void trace_tile(const KArgs& A, const FrameRec& F, ui
         if (!spilled) store_pixel(A, F, o, mk(clamp01(c.x), clamp01(c.y), clamp01(c.z)));
         return;
     }
-    if constexpr (SKY) {
-        // Sky table (sky_trace_kernel: triangle-free spp-1 frames without rays_in / out32, A.sky
-        // set): the primary rays are intersected here, and a wave whose rays all miss stores the
-        // words a primary miss of its pixels packs to (no frame of a launch with a table has a
-        // view, so its camera only translates and they are the same in every frame) and is done.  The load is issued before the tests and its
-        // word is dead after the ballot; any other wave hands its root hits to cast_seg (ROOT),
-        // and the missing lanes of a mixed tile take the per-ray background as before.
-        static_assert(!SKY || (GEOM == 0 && !COUNT && !SPLIT && !DEFER), "the sky table serves plain GEOM 0 frames");
-        {
-            const f3 d = primary_dir<false>(A, x, y, 0);
-            const uint32_t word = A.sky[(size_t)y * A.width + x];
-            Hit h;
-            scene_intersect<false, 0>(A, orig, d, h, cnt, slab);
-            if (__ballot(h.kind != HIT_NONE) == 0ull) {
-                if (F.out8) F.out8[out_index(A, F, o)] = word;
-                return;
-            }
-            bool unused = false;
-            const f3 c = cast_seg<CAP, false, 0, false, false, true, SMASK>(A, Seg{orig, d, 1.0f, 0}, cnt, lds, slab,
-                                                                           0u, unused, &h);
-            store_pixel(A, F, o, mk(clamp01(c.x), clamp01(c.y), clamp01(c.z))); // cast_ray's clamp
-            return;
-        }
-    }
     const uint32_t spp = A.spp ? A.spp : 1u;
     f3 acc = mk(0.0f, 0.0f, 0.0f);
     for (uint32_t s = 0; s < spp; ++s) {
@@ -2465,6 +2441,47 @@ __device__ __forceinline__ void trace_tile(const KArgs& A, const FrameRec& F, ui
     return;
 #endif
     store_pixel(A, F, o, acc);
+}
+
+// Sky table (the sky kernels: triangle-free spp-1 frames without rays_in / out32, A.sky set), one
+// frame of a tile that runs the trace (sky_tile), from its primary direction `d` and sky word on:
+// the primary rays are intersected here, and a wave whose rays all miss stores the words a primary
+// miss of its pixels packs to and is done.  The word is dead after the ballot; any other wave
+// hands its root hits to cast_seg (ROOT), and the missing lanes of a mixed tile take the per-ray
+// background as in trace_tile.
+template <int CAP, bool SMASK>
+__device__ __forceinline__ void sky_frame(const KArgs& A, const FrameRec& F, f3 d, uint32_t word, size_t o, Cnt& cnt,
+                                          float* lds, float4* slab) {
+    const f3 orig = mk(F.cam[0], F.cam[1], F.cam[2]);
+    Hit h;
+    scene_intersect<false, 0>(A, orig, d, h, cnt, slab);
+    if (__ballot(h.kind != HIT_NONE) == 0ull) {
+        if (F.out8) F.out8[out_index(A, F, o)] = word;
+        return;
+    }
+    bool unused = false;
+    const f3 c = cast_seg<CAP, false, 0, false, false, true, SMASK>(A, Seg{orig, d, 1.0f, 0}, cnt, lds, slab, 0u, unused, &h);
+    store_pixel(A, F, o, mk(clamp01(c.x), clamp01(c.y), clamp01(c.z))); // cast_ray's clamp
+}
+
+// A tile of a sky kernel that runs the trace (every tile in its span without the floor class, the
+// sphere-class tiles with it) in frames f .. f + nf - 1 of the launch (nf = 2 for a frame pair, else
+// 1): the primary direction and the sky word once per wave, as floor_tile has them (no frame of a
+// launch with a table has a view, so the camera only translates and both are the same in the two
+// frames).  Two calls, not a loop over the pair: the loop form is slower.
+template <int CAP, bool SMASK>
+__device__ __forceinline__ void sky_tile(const KArgs& A, uint32_t tile, uint32_t f, uint32_t nf, Cnt& cnt, float* lds,
+                                         float4* slab) {
+    const uint32_t lane = lane_id();
+    if (tile >= A.ntiles) return;
+    const uint32_t x = (tile % A.ntx) * 8u + (lane & 7u), k = (tile / A.ntx) * 8u + (lane >> 3);
+    if (x >= A.width || k >= A.rows) return;
+    const uint32_t y = band_row(A, k);
+    const size_t o = (size_t)k * A.width + x;
+    const f3 d = primary_dir<false>(A, x, y, 0);
+    const uint32_t word = A.sky[(size_t)y * A.width + x];
+    sky_frame<CAP, SMASK>(A, A.fr[f], d, word, o, cnt, lds, slab);
+    if (nf > 1u) sky_frame<CAP, SMASK>(A, A.fr[f + 1u], d, word, o, cnt, lds, slab);
 }
 
 // spp > 1 with one lane per SAMPLE (A.spp_lanes; spp a power of two in [2, 64]).  Wave `sub` of
@@ -2658,7 +2675,16 @@ __device__ __forceinline__ void trace_body(const KArgs& A) {
     // frame f = vb / ntiles of a multi-frame launch (plain frames only: split / deferred frames
     // and counting passes launch one frame)
     uint32_t f = 0, t = vb, tile;
-    if (!SPLIT && !DEFER && A.spp_lanes) { // one lane per sample: ntiles * spp waves per frame
+    // SKY: nf = 2 for a frame pair (frames f and f + 1), else 1; every way a sky kernel deals its
+    // tiles ends in the same span tests and the same floor_tile / sky_tile call below, so the
+    // kernel holds one copy of each.  (An index, not a pointer to the second frame: a pointer into
+    // A carried across the branches keeps the by-value KArgs copy alive, in scratch.)
+    uint32_t nf = 1u;
+    // the block took the pair path (its last pair may hold one frame): read by the clock build only,
+    // whose pair launches cull by their spans and write no records, as before
+    [[maybe_unused]] bool pair = false;
+    // (a sky kernel never runs one lane per sample: its launches have spp 1, launch_trace)
+    if (!SKY && !SPLIT && !DEFER && A.spp_lanes) { // one lane per sample: ntiles * spp waves per frame
         const uint32_t per = A.ntiles * A.spp;
         f = vb / per;
         const uint32_t r = vb - f * per;
@@ -2674,38 +2700,22 @@ __device__ __forceinline__ void trace_body(const KArgs& A) {
             // tiles cost nearly the same, so the pairs keep the waves balanced) — half the
             // workgroups, so half the per-workgroup launch and slot-refill overhead.  Two calls,
             // not a loop over a group size: the loop form compiled to a slower kernel (C2 13.8 ->
-            // 14.9 us per frame, profiles/r03_ab_frame_group_loop.log)
+            // 14.9 us per frame, profiles/r03_ab_frame_group_loop.log; again on the sky kernels,
+            // 8.60 -> 9.13, and 8.67 with the loop's hoisted kernel arguments kept out of the
+            // registers: profiles/one_body_ab_summary.txt)
             uint32_t pr;
             tile = inter_tile(A, vb, pr, (A.nframes + 1u) / 2u);
             f = 2u * pr;
-#ifndef TRT_DIAG_TRIVIAL
-            if constexpr (FLOORC) { // a pair never straddles two span tables (span_shift >= 1)
-                const uint32_t w = floor_span_word(A, tile, f), col = tile % A.ntx;
-                const FrameRec* F1 = f + 1u < A.nframes ? &A.fr[f + 1u] : nullptr;
-                if (floor_span_outside(col, w)) {
-                    sky_tile_store(A, tile, A.fr[f], F1);
-                    return;
-                }
-                if (floor_sphere_outside(col, w)) { // never for tile >= ntiles: its word is full
-#ifdef TRT_DIAG_FLOOR_SKY
-                    sky_tile_store(A, tile, A.fr[f], F1); // diagnostic build only: prices the floor class
-#else
-                    floor_tile(A, tile, A.fr[f], F1, cnt, slab);
-#endif
-                    return;
-                }
-            } else if constexpr (SPANS) {
-                if (span_outside(A, tile, span_word(A, tile, f))) {
-                    sky_tile_store(A, tile, A.fr[f], f + 1u < A.nframes ? &A.fr[f + 1u] : nullptr);
-                    return;
-                }
+            if constexpr (SKY) { // a pair never straddles two span tables (span_shift >= 1)
+                pair = true;
+                if (f + 1u < A.nframes) nf = 2u;
+            } else {
+                trace_tile<CAP, COUNT, GEOM, SPLIT, DEFER, HYB>(A, A.fr[f], tile, cnt, lds, slab, 0u, f);
+                if (f + 1u < A.nframes)
+                    trace_tile<CAP, COUNT, GEOM, SPLIT, DEFER, HYB>(A, A.fr[f + 1u], tile, cnt, lds, slab, 0u, f + 1u);
+                if (COUNT) flush_counts(A, cnt);
+                return;
             }
-#endif
-            trace_tile<CAP, COUNT, GEOM, SPLIT, DEFER, HYB, SKY, SMASK>(A, A.fr[f], tile, cnt, lds, slab, 0u, f);
-            if (f + 1u < A.nframes)
-                trace_tile<CAP, COUNT, GEOM, SPLIT, DEFER, HYB, SKY, SMASK>(A, A.fr[f + 1u], tile, cnt, lds, slab, 0u, f + 1u);
-            if (COUNT) flush_counts(A, cnt);
-            return;
         } else if (A.xcd_inter) {
             tile = inter_tile(A, vb, f, A.nframes);
         } else {
@@ -2755,30 +2765,45 @@ __device__ __forceinline__ void trace_body(const KArgs& A) {
     } else {
         tile = xcd_tile(A, t);
     }
-#if !defined(TRT_DIAG_TRIVIAL) && !defined(TRT_DIAG_WAVE_CLOCK)
+#ifndef TRT_DIAG_TRIVIAL
+#ifdef TRT_DIAG_WAVE_CLOCK
+    const bool cull = pair; // the clock build times every tile of a single-frame launch
+#else
+    constexpr bool cull = true;
+#endif
     if constexpr (FLOORC) {
         const uint32_t w = floor_span_word(A, tile, f), col = tile % A.ntx;
-        if (floor_span_outside(col, w)) {
-            sky_tile_store(A, tile, A.fr[f], nullptr);
+        if (cull && floor_span_outside(col, w)) {
+            sky_tile_store(A, tile, A.fr[f], nf > 1u ? &A.fr[f + 1u] : nullptr);
             return;
         }
-        if (floor_sphere_outside(col, w)) { // never for tile >= ntiles: its word is full
+        if (cull && floor_sphere_outside(col, w)) { // never for tile >= ntiles: its word is full
 #ifdef TRT_DIAG_FLOOR_SKY
-            sky_tile_store(A, tile, A.fr[f], nullptr);
+            sky_tile_store(A, tile, A.fr[f], nf > 1u ? &A.fr[f + 1u] : nullptr);
 #else
-            floor_tile(A, tile, A.fr[f], nullptr, cnt, slab);
+            floor_tile(A, tile, f, nf, cnt, slab);
 #endif
             return;
         }
     } else if constexpr (SPANS) {
-        if (span_outside(A, tile, span_word(A, tile, f))) {
-            sky_tile_store(A, tile, A.fr[f], nullptr);
+        if (cull && span_outside(A, tile, span_word(A, tile, f))) {
+            sky_tile_store(A, tile, A.fr[f], nf > 1u ? &A.fr[f + 1u] : nullptr);
             return;
         }
     }
 #endif
-    trace_tile<CAP, COUNT, GEOM, SPLIT, DEFER, HYB, SKY, SMASK>(A, A.fr[f], tile, cnt, lds, slab, 0u, f);
+#ifndef TRT_DIAG_TRIVIAL
+    if constexpr (SKY) { // the direction and the sky word once per pair
+        sky_tile<CAP, SMASK>(A, tile, f, nf, cnt, lds, slab);
+    } else
+#endif
+    {
+        trace_tile<CAP, COUNT, GEOM, SPLIT, DEFER, HYB>(A, A.fr[f], tile, cnt, lds, slab, 0u, f);
+        if constexpr (SKY)
+            if (nf > 1u) trace_tile<CAP, COUNT, GEOM, SPLIT, DEFER, HYB>(A, A.fr[f + 1u], tile, cnt, lds, slab, 0u, f + 1u);
+    }
 #ifdef TRT_DIAG_WAVE_CLOCK
+    if (pair) return; // pair launches write no records
     __syncthreads();
     // single-frame launches write the records to out32; multi-frame launches to the diagnostic
     // buffer (trt_diag_set_buffer), with the frame in bits 20-27
