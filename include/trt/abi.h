@@ -282,6 +282,81 @@ int trt_set_view(trt_ctx* ctx, const trt_view* v);
 int trt_render_frames_view(trt_ctx* ctx, const trt_params* p, const trt_ubo* ubos, const trt_view* views,
                            uint32_t nframes, uint8_t* out_rgba8, size_t frame_stride, uint32_t time_every);
 
+/* ---- ray queries: caller rays with their own origins, with hit records --------------------
+ * trt_render answers one question: what does the pinhole camera at camPos see.  A ray query
+ * traces `nrays` rays the caller made — picking, a panorama or stereo camera, rays leaving a
+ * surface — and can return, per ray, the colour and the nearest hit.
+ *
+ * What ray i is: the primary ray main() of the shader would trace from origin `org` in direction
+ * d = normalize(dir), the shader's own normalize (shader.comp:593) — exactly what the kernel does
+ * to a binding-1 direction.  The scene, UBO spheres and lights are the context's; camPos and the
+ * context's view are not read.
+ *
+ * Read from p: max_depth (1..20) and flags, of which SPHERES, FLOOR, CHECKER, ENVMAP, BATCH_WALK,
+ * SRGB_OUT, DEVICE_PTRS, COUNT and TIMING are honoured.  Every other field and flag is ignored.
+ *
+ * Outputs, any of which may be NULL (all three NULL: TRT_ERR_INVALID):
+ *   out_rgba8[i]        the storage-image word of the ray (RGBA8 = floor(255 * c + 0.5), a = 255);
+ *   out_rgba32f[4i..]   rayOut.resultColor = (gamma(c), 1);
+ *   hits[i]             the result of scene_intersect for the ray (shader.comp:295-362): t, what
+ *                       was hit and, for a triangle, the Moller-Trumbore weights u, v of v1, v2
+ *                       (the point is (1 - u - v) v0 + u v1 + v v2) and the caller's index into
+ *                       the binding-5 array; n is the shading normal before any facing flip:
+ *                       (0, 1, 0) for the floor, normalize(p - centre) for a sphere, the flat or
+ *                       interpolated normal for a triangle.  A miss is t = 1e10 (the shader's
+ *                       initial nearest distance), kind TRT_HIT_NONE, the rest 0.
+ * With both colour outputs NULL nothing is shaded: a pure nearest-hit query, max_depth unused
+ * (still range-checked).  TRT_FLAG_COUNT without a colour output is TRT_ERR_INVALID.
+ *
+ * A valid ray: all six floats finite, and s = (dx * dx + dy * dy) + dz * dz, in FP32 in that
+ * order, within [TRT_QRAY_MIN_LEN2, TRT_QRAY_MAX_LEN2], so the normalized direction is finite
+ * and of unit length.  The host checker and the kernel share one predicate.  A host-pointer call
+ * validates every ray before anything is launched: a bad ray returns TRT_ERR_INVALID with its
+ * index in trt_last_error and the outputs untouched.  A device-pointer call cannot be checked on
+ * the host, so the kernel treats a bad ray as inactive: it traces nothing and counts nothing,
+ * and writes RGBA8 word 0 (alpha 0), float4 0 and kind TRT_HIT_BAD_RAY with zeros elsewhere;
+ * the other rays of its wave are unaffected.
+ *
+ * Counting (TRT_FLAG_COUNT): the counters are those of cast_ray alone — the hit record's own
+ * intersection is not counted — and primary_rays is the number of valid rays.
+ *
+ * Stream and buffers as trt_render: with device pointers and no COUNT / TIMING the call only
+ * enqueues on the context's stream (trt_set_stream applies); host pointers are synchronous and
+ * go through context-owned staging buffers that only grow.  Device arrays are read and written
+ * as 16-byte vectors: with TRT_FLAG_DEVICE_PTRS `rays`, `hits` and `out_rgba32f` must be 16-byte
+ * aligned and `out_rgba8` 4-byte aligned, else TRT_ERR_INVALID (host arrays need only the
+ * alignment of their C types).  nrays == 0 is TRT_OK and launches
+ * nothing; nrays > TRT_QRAY_MAX_RAYS is TRT_ERR_INVALID.  Meshes are traced by the path
+ * trt_render takes for the scene (the BVH walk, or the batch walk with TRT_FLAG_BATCH_WALK).
+ * The call changes nothing a later trt_render depends on. */
+typedef struct trt_qray { float org[3]; float pad0; float dir[3]; float pad1; } trt_qray;  /* 32 B */
+typedef struct trt_qhit { float t; uint32_t kind; uint32_t index; float u, v; float n[3]; } trt_qhit; /* 32 B */
+#define TRT_HIT_NONE 0u      /* t = 1e10 (the shader's initial nearest), the rest 0 */
+#define TRT_HIT_FLOOR 1u
+#define TRT_HIT_SPHERE 2u    /* index 0..3 */
+#define TRT_HIT_TRIANGLE 3u  /* index into the caller's binding-5 array, u/v the Moller-Trumbore weights of v1/v2 */
+#define TRT_HIT_BAD_RAY 0xffffffffu
+#define TRT_QRAY_MIN_LEN2 1e-30f
+#define TRT_QRAY_MAX_LEN2 1e30f
+#define TRT_QRAY_MAX_RAYS (1u << 28)
+#ifdef __cplusplus
+static_assert(sizeof(trt_qray) == 32 && sizeof(trt_qhit) == 32, "query records are 32 B");
+#else
+_Static_assert(sizeof(trt_qray) == 32 && sizeof(trt_qhit) == 32, "query records are 32 B");
+#endif
+
+int trt_trace_rays(trt_ctx* ctx, const trt_params* p, const trt_qray* rays, uint32_t nrays,
+                   uint8_t* out_rgba8, float* out_rgba32f, trt_qhit* hits, trt_stats* st);
+/* host only, no context: TRT_OK when every ray is valid, else TRT_ERR_INVALID with the lowest bad
+ * index in *first_bad (may be NULL).  rays NULL with n > 0 is TRT_ERR_INVALID (*first_bad = 0). */
+int trt_check_rays(const trt_qray* rays, uint32_t n, uint32_t* first_bad);
+/* host only, no context: steps 1 and 2 of the view contract above for pixel (x, y) at spp 1, row
+ * quirk honoured, v NULL = the reference camera: out->dir = w, out->org = cam, pads 0.  The
+ * single-pixel twin of trt_view_rays, bit for bit.  TRT_ERR_INVALID for a null argument, a bad
+ * image size or a pixel outside the image. */
+int trt_pixel_ray(const trt_params* p, const trt_view* v, const float cam[3],
+                  uint32_t x, uint32_t y, trt_qray* out);
+
 /* Device time per frame (ms) of each launch timed by the last timed trt_render_frames call:
  * the launch's event span divided by the frames it traced (waits for them); n <= the number
  * of timed launches, trt_timed_launches(). */

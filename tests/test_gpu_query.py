@@ -1,0 +1,470 @@
+"""Ray queries on the GPU (abi.h trt_trace_rays, ray_query_kernel): pinhole rays reproduce the
+frame bit for bit, free rays match the CPU oracle's cast_ray, hit records match records built by
+the shader's own order from the oracle's single-ray probes, bad rays are inert, sizes keep their
+bounds, and a query leaves every later frame as it was."""
+from __future__ import annotations
+
+import ctypes
+
+import numpy as np
+import pytest
+
+from oracle import oracle as orc
+from tests.helpers import assert_float_close, assert_rgba8_close
+from vkcomputeshader_tinyraytracer_amd import TrtError, scene as S, types as T
+
+pytestmark = pytest.mark.gpu
+
+f32 = np.float32
+W, H = 71, 41  # 2,911 rays: 45 full waves and one of 31 lanes
+EPS = f32(0.0001)  # MIN_EPSILON, shader.comp:78
+V1 = S.view_ypr(20, -10, 5)
+CAM_OFF = (1.5, 0.75, 2.0)
+
+
+@pytest.fixture(scope="module")
+def scenes():
+    c2 = S.config_c2(W, H, env_size=(64, 32))
+    c3 = S.config_c3(W, H, env_size=(64, 32), level=2)  # a 320-triangle glass icosphere
+    return {"C2": c2, "C3": c3}
+
+
+@pytest.fixture(scope="module")
+def bound(scenes):
+    return {k: orc._Bound(sc) for k, sc in scenes.items()}
+
+
+@pytest.fixture
+def use(gpu_renderer):
+    """Uploads a scene into the session's context and hands it back in its default state."""
+    r = gpu_renderer
+
+    def _use(sc, cam=(0.0, 0.0, 0.0), view=None):
+        if r.scene is not sc:
+            r.upload_scene(sc)
+        r.update_ubo(S.make_ubo(cam=cam))
+        r.set_view(view)
+        return r
+
+    yield _use
+    r.set_view(None)
+    r.set_stream(None)
+    if r.scene is not None:
+        r.update_ubo(r.scene.ubo)
+
+
+def normalize32(v):
+    """The shader's normalize in float32 numpy: v * (1 / sqrt((x x + y y) + z z))."""
+    v = np.asarray(v, f32)
+    inv = f32(1) / np.sqrt((v[..., 0] * v[..., 0] + v[..., 1] * v[..., 1]) + v[..., 2] * v[..., 2])
+    return v * inv[..., None]
+
+
+def random_rays(n: int, seed: int) -> np.ndarray:
+    """Origins uniform in x [-8, 8], y [-3, 6], z [-28, 2] (inside the spheres and the mesh
+    included); directions uniform on the sphere times a length in [0.1, 10]."""
+    rng = np.random.default_rng(seed)
+    q = np.zeros(n, T.QRAY)
+    q["org"] = rng.uniform((-8, -3, -28), (8, 6, 2), size=(n, 3)).astype(f32)
+    d = rng.normal(size=(n, 3))
+    d /= np.linalg.norm(d, axis=1, keepdims=True)
+    q["dir"] = (d * rng.uniform(0.1, 10.0, size=(n, 1))).astype(f32)
+    return q
+
+
+def exact(st: dict) -> dict:
+    return {k: st[k] for k in T.Stats.EXACT}
+
+
+def fa(v):
+    return (ctypes.c_float * len(v))(*[float(x) for x in v])
+
+
+# ---- A: pinhole equivalence, bit for bit ------------------------------------------------------
+
+
+@pytest.mark.parametrize("view,cam", [(None, (0.0, 0.0, 0.0)), (V1, (0.0, 0.0, 0.0)), (None, CAM_OFF), (V1, CAM_OFF)],
+                         ids=["identity", "V1", "identity-off", "V1-off"])
+@pytest.mark.parametrize("name,depth", [("C2", 1), ("C2", 4), ("C2", 20), ("C3", 4), ("C3", 8)])
+def test_pinhole_rays_equal_the_frame(use, scenes, name, depth, view, cam):
+    sc = scenes[name]
+    r = use(sc, cam, view)
+    p = sc.params(max_depth=depth)
+    want8, want32, wst = r.draw_frame(p, count=True, want32=True)
+    rays = S.pinhole_qrays(p, view, cam).reshape(-1)
+    c8, c32, _, cst = r.trace_rays(rays, p, count=True, want32=True)
+    assert c8.tobytes() == want8.reshape(-1, 4).tobytes()
+    assert c32.tobytes() == want32.reshape(-1, 4).tobytes()
+    assert exact(cst) == exact(wst) and cst["primary_rays"] == W * H
+    g8, g32, ghits, gst = r.trace_rays(rays, p, want32=True, want_hits=True)
+    assert g8.tobytes() == c8.tobytes() and g32.tobytes() == c32.tobytes()
+    assert gst["primary_rays"] == 0  # no COUNT flag, no counters
+    # the same rays in a seeded random order: every lane's answer is its own
+    perm = np.random.default_rng(7 + depth).permutation(len(rays))
+    s8, s32, shits, _ = r.trace_rays(rays[perm], p, want32=True, want_hits=True)
+    inv = np.argsort(perm)
+    assert s8[inv].tobytes() == g8.tobytes() and s32[inv].tobytes() == g32.tobytes()
+    assert shits[inv].tobytes() == ghits.tobytes()
+
+
+# ---- B: free rays against the oracle ----------------------------------------------------------
+
+
+def oracle_colours(b, p, rays):
+    """Per ray: the oracle's cast_ray from the ray's origin along the float32-normalized direction;
+    its clamped linear colour through the shader's gamma and pack.  Returns (rgba8, rgba32f, summed
+    counters)."""
+    L = orc.lib()
+    d = normalize32(rays["dir"])
+    n = len(rays)
+    lin = np.zeros((n, 3), f32)
+    tot = {k: 0 for k in T.Stats.EXACT_WALK}
+    out = (ctypes.c_float * 3)()
+    st = T.Stats()
+    for i in range(n):
+        L.orc_cast_ray(ctypes.byref(b.s), ctypes.byref(p), orc.MODE_FAST, fa(rays["org"][i]), fa(d[i]), out,
+                       ctypes.byref(st))
+        lin[i] = out[:]
+        for k in tot:
+            tot[k] += int(getattr(st, k))
+    g = np.power(lin, f32(2.2)).astype(f32)
+    ref32 = np.concatenate([g, np.ones((n, 1), f32)], 1)
+    ref8 = np.concatenate([np.floor(f32(255) * g + f32(0.5)).astype(np.uint8), np.full((n, 1), 255, np.uint8)], 1)
+    return ref8, ref32, tot
+
+
+@pytest.mark.parametrize("name,depth,rayset,n", [("C2", 4, "random", 4099), ("C3", 4, "random", 4099),
+                                                 ("C3", 20, "random", 1027), ("C2", 4, "equirect", 64 * 32)],
+                         ids=["C2-d4", "C3-d4", "C3-d20", "C2-equirect"])
+def test_free_rays_match_the_oracle(use, scenes, bound, name, depth, rayset, n):
+    sc = scenes[name]
+    r = use(sc)
+    p = sc.params(max_depth=depth)
+    rays = random_rays(n, 1000 + n + depth) if rayset == "random" else S.equirect_qrays(64, 32, (0.5, 1.0, -9.0)).reshape(-1)
+    assert len(rays) == n
+    ref8, ref32, tot = oracle_colours(bound[name], p, rays)
+    g8, g32, _, st = r.trace_rays(rays, p, count=True, want32=True)
+    rep = assert_rgba8_close(g8, ref8)
+    err = assert_float_close(g32, ref32)
+    print(f"{name} depth {depth}, {len(rays)} rays: rgba8 {rep}, rayOut max |d| {err:.3g}")
+    # geometry is bit-exact under the arithmetic contract: the counters are the oracle's
+    assert exact(st) == exact(tot)
+
+
+# ---- C: hit records ---------------------------------------------------------------------------
+
+
+def expected_hits(sc, rays):
+    """scene_intersect in the shader's own order with a strict `<` throughout: the floor
+    (shader.comp:302-320 restated in float32 numpy), the spheres 0..3 (orc_ray_sphere), then every
+    batch in order behind orc_ray_aabb with orc_ray_triangle over its triangles."""
+    L = orc.lib()
+    spheres = [np.asarray(sc.ubo[f"sphere{i}"]["center_radius"], f32) for i in range(4)]
+    sph_c = [fa(s) for s in spheres]
+    tri_c = [[fa(sc.tris[k][j][:3]) for k in ("v0", "v1", "v2", "v0_norm", "v1_norm", "v2_norm")] for j in range(len(sc.tris))]
+    boxes = [(fa(m["bboxMin"][:3]), fa(m["bboxMax"][:3]), int(m["params0"][0]), int(m["params0"][1]), int(m["params0"][2]))
+             for m in sc.models]
+    dirs = normalize32(rays["dir"])
+    out = np.zeros(len(rays), T.QHIT)
+    t = ctypes.c_float(0)
+    nrm = (ctypes.c_float * 3)()
+    for i in range(len(rays)):
+        o, d = rays["org"][i], dirs[i]
+        oc, dc = fa(o), fa(d)
+        best, kind, idx, n = f32(1e10), T.HIT_NONE, 0, np.zeros(3, f32)
+        if sc.flags & T.FLAG_FLOOR and abs(d[1]) > EPS:
+            tf = -(o[1] + f32(4.0)) / d[1]
+            if tf > EPS and tf < best:
+                pt = o + d * tf
+                if abs(pt[0]) < f32(10.0) and pt[2] < f32(-5.0) and pt[2] > f32(-30.0):
+                    best, kind, n = tf, T.HIT_FLOOR, np.array((0, 1, 0), f32)
+        if sc.flags & T.FLAG_SPHERES:
+            for s in range(4):
+                if L.orc_ray_sphere(oc, dc, sph_c[s], ctypes.byref(t)) and f32(t.value) < best:
+                    best, kind, idx = f32(t.value), T.HIT_SPHERE, s
+                    n = normalize32((o + d * best) - spheres[s][:3])
+        for bmin, bmax, start, count, ni in boxes:
+            if not L.orc_ray_aabb(oc, dc, bmin, bmax):
+                continue
+            for j in range(start, start + count):
+                if L.orc_ray_triangle(oc, dc, *tri_c[j], ni, ctypes.byref(t), nrm) and f32(t.value) > EPS and f32(t.value) < best:
+                    best, kind, idx, n = f32(t.value), T.HIT_TRIANGLE, j, np.array(nrm[:], f32)
+        out[i]["t"], out[i]["kind"], out[i]["index"], out[i]["n"] = best, kind, idx, n
+    return out
+
+
+@pytest.mark.parametrize("name", ["C3", "C2"])
+def test_hit_records(use, scenes, name):
+    sc = scenes[name]
+    r = use(sc)
+    p = sc.params()
+    rays = random_rays(2053, 77)
+    want = expected_hits(sc, rays)
+    _, _, got, _ = r.trace_rays(rays, p, want8=False, want_hits=True)  # hits only
+    kinds = {k: int((want["kind"] == k).sum()) for k in (T.HIT_NONE, T.HIT_FLOOR, T.HIT_SPHERE, T.HIT_TRIANGLE)}
+    print(f"{name}: expected kinds {kinds}")
+    assert kinds[T.HIT_NONE] and kinds[T.HIT_FLOOR] and kinds[T.HIT_SPHERE] and (name == "C2" or kinds[T.HIT_TRIANGLE])
+    for k in ("t", "kind", "index", "n"):
+        assert got[k].tobytes() == want[k].tobytes(), k
+    miss = got[got["kind"] == T.HIT_NONE]
+    assert (miss["t"] == f32(1e10)).all() and not miss["index"].any() and not miss["u"].any() and not miss["v"].any()
+    assert not miss["n"].any()
+    nontri = got[got["kind"] != T.HIT_TRIANGLE]
+    assert not nontri["u"].any() and not nontri["v"].any()
+    # barycentrics: u, v weigh v1, v2, and the weighted vertices are the hit point
+    tri = np.flatnonzero(got["kind"] == T.HIT_TRIANGLE)
+    d = normalize32(rays["dir"]).astype(np.float64)
+    for i in tri:
+        tr, u, v = sc.tris[got["index"][i]], float(got["u"][i]), float(got["v"][i])
+        pb = (1 - u - v) * tr["v0"][:3].astype(np.float64) + u * tr["v1"][:3] + v * tr["v2"][:3]
+        pr = rays["org"][i].astype(np.float64) + d[i] * float(got["t"][i])
+        assert np.abs(pb - pr).max() <= 1e-4 * max(1.0, np.abs(pr).max()), (i, pb, pr)
+    # a call that also shades returns the same records
+    _, _, both, _ = r.trace_rays(rays, p, want8=True, want32=True, want_hits=True)
+    assert both.tobytes() == got.tobytes()
+
+
+def test_pick_is_the_pixel_record(use, scenes):
+    sc = scenes["C2"]
+    p = sc.params()
+    for view, cam in ((None, (0.0, 0.0, 0.0)), (V1, CAM_OFF)):
+        r = use(sc, cam, view)
+        rays = S.pinhole_qrays(p, view, cam).reshape(-1)
+        _, _, hits, _ = r.trace_rays(rays, p, want8=False, want_hits=True)
+        grid = hits.reshape(H, W)
+        pixels = [(W - 1, 0), (W - 1, H // 2), (0, 0)]  # the last column (row quirk) and a corner
+        for kind in (T.HIT_SPHERE, T.HIT_FLOOR, T.HIT_NONE):
+            ys, xs = np.nonzero(grid["kind"] == kind)
+            assert len(ys), kind
+            pixels.append((int(xs[len(xs) // 2]), int(ys[len(ys) // 2])))
+        for x, y in pixels:
+            assert r.pick(p, x, y).tobytes() == grid[y, x].tobytes(), (x, y)
+    with pytest.raises(TrtError):
+        r.pick(p, W, 0)
+
+
+def test_pick_follows_the_camera_of_a_frame_loop(use, scenes):
+    """trt_render_frames leaves the context's UBO at its last frame's: a pick after a camera walk
+    is the pixel's record from the walk's last camPos, through render_frames and frames_call."""
+    torch = pytest.importorskip("torch")
+    sc = scenes["C2"]
+    r = use(sc)
+    p = sc.params()
+    out = torch.zeros((5, H, W, 4), dtype=torch.uint8, device=f"cuda:{r.device}")
+    torch.cuda.synchronize(r.device)
+    for speed, via_call in ((0.4, False), (0.7, True)):
+        ubos = S.camera_path(sc.ubo, 5, speed)
+        if via_call:
+            r.frames_call(p, out, 5, ubos=ubos, frame_stride=H * W * 4)()
+        else:
+            r.render_frames(p, out, 5, ubos=ubos, frame_stride=H * W * 4)
+        r.synchronize()
+        cam = tuple(ubos[4]["camPos"][:3])
+        assert cam != (0.0, 0.0, 0.0)
+        rays = S.pinhole_qrays(p, None, cam).reshape(-1)
+        grid = r.trace_rays(rays, p, want8=False, want_hits=True)[2].reshape(H, W)
+        stale = r.trace_rays(S.pinhole_qrays(p).reshape(-1), p, want8=False, want_hits=True)[2].reshape(H, W)
+        pixels = [(x, y) for y in range(0, H, 5) for x in range(0, W, 7)]
+        assert any(grid[y, x].tobytes() != stale[y, x].tobytes() for x, y in pixels)  # the walk moved what is seen
+        for x, y in pixels:
+            assert r.pick(p, x, y).tobytes() == grid[y, x].tobytes(), (x, y)
+        # and the frame drawn now is the frame of that camera
+        assert r.draw_frame(p)[0].tobytes() == out[4].cpu().numpy().tobytes()
+
+
+# ---- the other mesh paths: the batch walk (GEOM 1) and the unquantized BVH (GEOM 2) ---------------
+
+
+@pytest.fixture(scope="module")
+def c3_refs(scenes, bound):
+    """One ray set on C3 at depth 4 with its oracle colours, counters and expected records, shared by
+    the mesh paths.  Half the rays start near the mesh and aim at it, so triangles are well hit."""
+    sc = scenes["C3"]
+    rays = random_rays(1027, 4242)
+    rng = np.random.default_rng(99)
+    aim = np.arange(0, len(rays), 2)
+    rays["org"][aim] = (np.array((2.5, -2.0, -10.0)) + rng.uniform(-4, 4, size=(len(aim), 3))).astype(f32)
+    rays["dir"][aim] = (np.array((2.5, -2.0, -10.0)) + rng.uniform(-1.2, 1.2, size=(len(aim), 3)) - rays["org"][aim]).astype(f32)
+    ref8, ref32, tot = oracle_colours(bound["C3"], sc.params(), rays)
+    want = expected_hits(sc, rays)
+    assert int((want["kind"] == T.HIT_TRIANGLE).sum()) > 100
+    return rays, ref8, ref32, tot, want
+
+
+def _check_mesh_path(r, sc, p, refs, counters):
+    rays, ref8, ref32, tot, want = refs
+    g8, g32, hits, st = r.trace_rays(rays, p, count=True, want32=True, want_hits=True)
+    assert_rgba8_close(g8, ref8)
+    assert_float_close(g32, ref32)
+    assert {k: st[k] for k in counters} == {k: tot[k] for k in counters}
+    for k in ("t", "kind", "index", "n"):
+        assert hits[k].tobytes() == want[k].tobytes(), k
+    _, _, only, _ = r.trace_rays(rays, p, want8=False, want_hits=True)
+    assert only.tobytes() == hits.tobytes()
+    return g8, g32, hits
+
+
+def test_mesh_paths_agree(use, scenes, c3_refs, monkeypatch):
+    """The query kernels of every mesh path against the same references: the quantized BVH the
+    scene takes by default (GEOM 3), the reference-order batch walk (TRT_FLAG_BATCH_WALK, GEOM 1:
+    it also tests exactly the reference's batches and triangles) and the unquantized BVH (GEOM 2,
+    a context created with TRT_BVH_WAVES4=0)."""
+    from vkcomputeshader_tinyraytracer_amd import Renderer
+
+    sc = scenes["C3"]
+    r = use(sc)
+    p = sc.params()
+    a = _check_mesh_path(r, sc, p, c3_refs, T.Stats.EXACT)
+    b = _check_mesh_path(r, sc, sc.params(flags=sc.flags | T.FLAG_BATCH_WALK), c3_refs, T.Stats.EXACT_WALK)
+    monkeypatch.setenv("TRT_BVH_WAVES4", "0")
+    with Renderer(r.device) as r2:
+        r2.upload_scene(sc)
+        c = _check_mesh_path(r2, sc, p, c3_refs, T.Stats.EXACT)
+    monkeypatch.delenv("TRT_BVH_WAVES4")
+    for other in (b, c):  # and bit for bit with each other
+        for x, y in zip(a, other):
+            assert x.tobytes() == y.tobytes()
+
+
+# ---- D: bad rays ------------------------------------------------------------------------------
+
+
+def test_bad_rays_are_inert_on_the_device_and_rejected_on_the_host(use, scenes):
+    torch = pytest.importorskip("torch")
+    sc = scenes["C3"]
+    r = use(sc)
+    p = sc.params()
+    good = random_rays(130, 5)
+    bad = good.copy()
+    bad["dir"][0] = (np.nan, 0.0, -1.0)
+    bad["dir"][63] = 0.0
+    bad["org"][64, 1] = np.inf
+    bad["dir"][129] = (3e19, 0.0, 0.0)
+    lanes = [0, 63, 64, 129]
+    rest = np.setdiff1d(np.arange(130), lanes)
+    w8, w32, whits, _ = r.trace_rays(good, p, want32=True, want_hits=True)
+
+    dev = torch.from_numpy(bad.view(np.uint8).reshape(130, 32)).to(f"cuda:{r.device}")
+    torch.cuda.synchronize(r.device)
+    g8, g32, ghits, st = r.trace_rays(dev, p, count=True, want32=True, want_hits=True)
+    g8, g32 = g8.cpu().numpy(), g32.cpu().numpy()
+    ghits = ghits.cpu().numpy().view(T.QHIT).reshape(-1)
+    assert not g8[lanes].any() and not g32[lanes].any()
+    assert (ghits["kind"][lanes] == T.HIT_BAD_RAY).all()
+    for k in ("t", "index", "u", "v", "n"):
+        assert not ghits[k][lanes].any(), k
+    assert g8[rest].tobytes() == w8[rest].tobytes() and g32[rest].tobytes() == w32[rest].tobytes()
+    assert ghits[rest].tobytes() == whits[rest].tobytes()
+    assert st["primary_rays"] == 126
+
+    o8 = np.full((130, 4), 0xA5, np.uint8)
+    o32 = np.full((130, 4), -7.0, f32)
+    oh = np.zeros(130, T.QHIT)
+    oh["index"] = 0xABCD
+    with pytest.raises(TrtError, match=r"ray 0 ") as e:
+        r.trace_rays(bad, p, out8=o8, out32=o32, hits=oh)
+    assert e.value.code == T.TRT_ERR_INVALID
+    assert (o8 == 0xA5).all() and (o32 == -7.0).all() and (oh["index"] == 0xABCD).all() and not oh["t"].any()
+
+
+# ---- E: sizes ---------------------------------------------------------------------------------
+
+
+def test_sizes_keep_their_bounds(use, scenes):
+    torch = pytest.importorskip("torch")
+    sc = scenes["C3"]
+    r = use(sc)
+    p = sc.params()
+    rays = random_rays(130, 11)
+    w8, w32, whits, _ = r.trace_rays(rays, p, want32=True, want_hits=True)
+    dev = torch.from_numpy(rays.view(np.uint8).reshape(130, 32)).to(f"cuda:{r.device}")
+    for n in (0, 1, 63, 64, 65):
+        o8 = torch.full((n + 64, 4), 0xA5, dtype=torch.uint8, device=dev.device)
+        o32 = torch.full((n + 64, 4), -7.0, dtype=torch.float32, device=dev.device)
+        oh = torch.full((n + 64, 32), 0x5A, dtype=torch.uint8, device=dev.device)
+        torch.cuda.synchronize(r.device)
+        r.trace_rays(dev, p, out8=o8, out32=o32, hits=oh, nrays=n)
+        r.synchronize()
+        o8, o32, oh = o8.cpu().numpy(), o32.cpu().numpy(), oh.cpu().numpy()
+        assert o8[:n].tobytes() == w8[:n].tobytes() and o32[:n].tobytes() == w32[:n].tobytes(), n
+        assert oh[:n].tobytes() == whits[:n].tobytes(), n
+        assert (o8[n:] == 0xA5).all() and (o32[n:] == -7.0).all() and (oh[n:] == 0x5A).all(), n
+        # the host path of the same size
+        h8, h32, hh, _ = r.trace_rays(rays[:n], p, want32=True, want_hits=True)
+        assert h8.tobytes() == w8[:n].tobytes() and h32.tobytes() == w32[:n].tobytes() and hh.tobytes() == whits[:n].tobytes()
+    with pytest.raises(TrtError):  # no output at all
+        r.trace_rays(rays, p, want8=False)
+    with pytest.raises(TrtError):  # counters need a colour output
+        r.trace_rays(rays, p, count=True, want8=False, want_hits=True)
+    for depth in (0, 21):
+        with pytest.raises(TrtError):
+            r.trace_rays(rays, sc.params(max_depth=depth))
+    with pytest.raises(TrtError):  # NULL rays
+        r.trace_rays(None, p, nrays=3)
+    # device arrays are moved as 16-byte vectors: an offset view is refused, not traced
+    raw = torch.zeros(32 * 8 + 16, dtype=torch.uint8, device=dev.device)
+    off = raw[4:4 + 32 * 8]
+    assert off.data_ptr() % 16 == 4
+    with pytest.raises(TrtError, match="16-byte aligned"):
+        r.trace_rays(off, p)
+    with pytest.raises(TrtError, match="16-byte aligned"):
+        r.trace_rays(dev, p, hits=off, nrays=8)
+    with pytest.raises(TrtError, match="16-byte aligned"):
+        r.trace_rays(dev, p, want8=False, out32=off.view(torch.float32), nrays=8)
+    assert r.trace_rays(None, p)[0].shape == (0, 4)  # nrays == 0 is fine, and launches nothing
+
+
+# ---- F: stream and state ----------------------------------------------------------------------
+
+
+def test_query_on_a_torch_stream(use, scenes):
+    torch = pytest.importorskip("torch")
+    sc = scenes["C3"]
+    r = use(sc)
+    p = sc.params()
+    rays = random_rays(1000, 3)
+    w8, w32, whits, _ = r.trace_rays(rays, p, want32=True, want_hits=True)
+    dev = torch.from_numpy(rays.view(np.uint8).reshape(-1, 32)).to(f"cuda:{r.device}")
+    torch.cuda.synchronize(r.device)
+    s = torch.cuda.Stream(device=r.device)
+    r.set_stream(s)
+    try:
+        with torch.cuda.stream(s):
+            g8, g32, gh, _ = r.trace_rays(dev, p, want32=True, want_hits=True)
+            g8, g32, gh = g8.cpu(), g32.cpu(), gh.cpu()  # on s, after the query
+        s.synchronize()
+    finally:
+        r.set_stream(None)
+    assert g8.numpy().tobytes() == w8.tobytes() and g32.numpy().tobytes() == w32.tobytes()
+    assert gh.numpy().tobytes() == whits.tobytes()
+
+
+def test_a_query_leaves_later_frames_as_they_were(use, scenes):
+    torch = pytest.importorskip("torch")
+    sc = scenes["C2"]
+    r = use(sc)
+    p = sc.params()
+    ubos = S.camera_path(sc.ubo, 20, 0.05)
+
+    def frames():
+        r.set_view(None)
+        r.update_ubo(sc.ubo)
+        one, _, _ = r.draw_frame(p)  # the plain C2 frame: sky table, spans, masks, floor class
+        out = torch.zeros((20, H, W, 4), dtype=torch.uint8, device=f"cuda:{r.device}")
+        torch.cuda.synchronize(r.device)
+        r.render_frames(p, out, 20, ubos=ubos, frame_stride=H * W * 4)
+        r.synchronize()
+        r.update_ubo(sc.ubo)
+        r.set_view(V1)
+        turned, _, _ = r.draw_frame(p)
+        r.set_view(None)
+        return one.tobytes(), out.cpu().numpy().tobytes(), turned.tobytes()
+
+    before = frames()
+    rays = random_rays(3000, 9)
+    r.trace_rays(rays, p, count=True, want32=True, want_hits=True)
+    dev = torch.from_numpy(rays.view(np.uint8).reshape(-1, 32)).to(f"cuda:{r.device}")
+    torch.cuda.synchronize(r.device)
+    r.trace_rays(dev, sc.params(max_depth=20), want_hits=True)
+    r.synchronize()
+    assert frames() == before

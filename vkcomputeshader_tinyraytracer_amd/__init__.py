@@ -18,8 +18,10 @@ from .scene import (
     config_c5,
     config_readme,
     config_reference_default,
+    equirect_qrays,
     icosphere,
     make_ubo,
+    pinhole_qrays,
     synthetic_envmap,
     view_look,
     view_rays,
@@ -30,5 +32,5 @@ __all__ = [
     "types", "ABI_SYMBOLS", "LIB_PATH", "TrtError", "lib", "Renderer", "render", "CONFIGS",
     "MODEL_INFOS", "Scene", "SceneBuilder", "camera_path", "config_c1", "config_c2", "config_c3", "config_c4",
     "config_c5", "config_readme", "config_reference_default", "icosphere", "make_ubo", "synthetic_envmap", "write_image",
-    "camera_orbit", "view_look", "view_rays", "view_ypr",
+    "camera_orbit", "view_look", "view_rays", "view_ypr", "pinhole_qrays", "equirect_qrays",
 ]

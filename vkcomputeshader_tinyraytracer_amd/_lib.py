@@ -81,6 +81,9 @@ def lib() -> ctypes.CDLL:
         "trt_view_rays": (c_int, [ctypes.POINTER(Params), vp, vp]),
         "trt_set_view": (c_int, [vp, vp]),
         "trt_render_frames_view": (c_int, [vp, ctypes.POINTER(Params), vp, vp, c_u32, vp, ctypes.c_size_t, c_u32]),
+        "trt_trace_rays": (c_int, [vp, ctypes.POINTER(Params), vp, c_u32, vp, vp, vp, ctypes.POINTER(Stats)]),
+        "trt_check_rays": (c_int, [vp, c_u32, ctypes.POINTER(c_u32)]),
+        "trt_pixel_ray": (c_int, [ctypes.POINTER(Params), vp, f3, c_u32, c_u32, vp]),
         "trt_frame_times": (c_int, [vp, ctypes.POINTER(ctypes.c_float), c_u32]),
         "trt_timed_launches": (c_u32, [vp, ctypes.POINTER(c_u32), c_u32]),
         "trt_set_frame_batch": (c_int, [vp, c_u32]),
@@ -164,6 +167,9 @@ ABI_SYMBOLS = (
     "trt_view_rays",
     "trt_set_view",
     "trt_render_frames_view",
+    "trt_trace_rays",
+    "trt_check_rays",
+    "trt_pixel_ray",
     "trt_frame_times",
     "trt_timed_launches",
     "trt_set_frame_batch",

@@ -93,6 +93,12 @@ struct trt_ctx {
     size_t cap32 = 0;
     void* d_rays = nullptr;
     size_t caprays = 0;
+    // trt_trace_rays with host pointers: the staged ray and hit records (its colours stage
+    // through d_out8 / d_out32); grow-only like the others
+    void* d_qrays = nullptr;
+    size_t capqrays = 0;
+    void* d_qhits = nullptr;
+    size_t capqhits = 0;
     unsigned long long* d_counters = nullptr;
     uint32_t num_cus = 256;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;

@@ -34,6 +34,7 @@
 #include "trt_bands.h"
 #include "trt_device.h"
 #include "trt_math.h"
+#include "trt_qray.h"
 
 namespace trt {
 
@@ -3166,6 +3167,98 @@ hipError_t launch_shadow_batch(const KArgs& A0, const float4* rays, uint32_t n, 
     else hipLaunchKernelGGL(shadow_batch_kernel<3>, grid, block, 0, stream, A, rays, n, occ);
     return hipGetLastError();
 }
+
+// Ray queries (abi.h trt_trace_rays): one lane per caller ray, 64 consecutive records per
+// one-wave workgroup (block b takes rays [64 b, 64 b + 64): two 16-byte loads per lane, 2 KB
+// contiguous per wave).  It is the general per-pixel loop with a per-lane origin: nothing that is
+// derived per frame from a wave-uniform camera (FrameRec.cam, the sky table, spans, occluder
+// masks, floor class) is read here, and A.fr / A.rays_in / A.out32 are not used — the outputs are
+// kernel parameters.  A lane whose record fails the shared predicate (trt_qray.h) traces and
+// counts nothing and writes the bad-ray record; its wave-mates go on (one wave per workgroup, so a
+// lane leaving early holds nobody at the LDS barriers, as in trace_tile).
+// hits: scene_intersect<false> (never counted) and resolve_hit's normal, two 16-byte stores.
+// SHADE: cast_ray from the lane's origin, then store_pixel's gamma, pack and stores.
+template <int CAP, bool COUNT, int GEOM, bool SHADE>
+__global__ __launch_bounds__(64, (trace_waves<GEOM, CAP, false, false>())) void ray_query_kernel(
+    KArgs A, const float4* __restrict__ rays, uint32_t n, uint32_t* __restrict__ out8, float4* __restrict__ out32,
+    uint4* __restrict__ hits) {
+    static_assert(SHADE || !COUNT, "a hits-only query counts nothing");
+    __shared__ float lds[SHADE ? lds_stack_floats<CAP, GEOM, false>() : 1];
+    __shared__ float4 slab[slab_float4s<GEOM>()];
+    const uint32_t i = blockIdx.x * 64u + threadIdx.x;
+    Cnt cnt;
+    // one pass of a loop, so a lane that is done leaves by `break` and every lane of the wave,
+    // lane 0 included, still reaches flush_counts (its wave_sum reads all 64 lanes)
+    for (bool once = i < n; once; once = false) {
+        const float4 ro = rays[2 * (size_t)i], rd = rays[2 * (size_t)i + 1];
+        if (!qray_valid(ro.x, ro.y, ro.z, rd.x, rd.y, rd.z)) {
+            if (hits) {
+                hits[2 * (size_t)i] = make_uint4(0u, TRT_HIT_BAD_RAY, 0u, 0u);
+                hits[2 * (size_t)i + 1] = make_uint4(0u, 0u, 0u, 0u);
+            }
+            if (SHADE && out32) out32[i] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+            if (SHADE && out8) out8[i] = 0u;
+            break;
+        }
+        const f3 o = mk(ro.x, ro.y, ro.z);
+        const f3 d = normalize3(mk(rd.x, rd.y, rd.z)); // shader.comp:593
+        if (hits) {
+            Hit h;
+            Cnt none;
+            scene_intersect<false, GEOM>(A, o, d, h, none, slab);
+            f3 nn = mk(0.0f, 0.0f, 0.0f);
+            if (h.kind != HIT_NONE) nn = resolve_hit<false>(A, Seg{o, d, 1.0f, 0}, h, none).n;
+            // Hit::idx of a triangle is the caller's binding-5 index for every GEOM: the BVH-ordered
+            // records carry it (TriGeo::pad[0]; a spatial split may reference one triangle twice)
+            // and A.geo / A.shade are in the caller's order; u, v weigh v1, v2 (e1 = v1 - v0, e2 =
+            // v2 - v0)
+            hits[2 * (size_t)i] =
+                make_uint4(__float_as_uint(h.t), (uint32_t)h.kind, (uint32_t)h.idx, __float_as_uint(h.u));
+            hits[2 * (size_t)i + 1] =
+                make_uint4(__float_as_uint(h.v), __float_as_uint(nn.x), __float_as_uint(nn.y), __float_as_uint(nn.z));
+        }
+        if constexpr (SHADE) {
+            const f3 c = cast_ray<CAP, COUNT, GEOM>(A, o, d, cnt, lds, slab);
+            cnt.pri += 1;
+            const f3 g = gamma3(c);
+            if (out32) out32[i] = make_float4(g.x, g.y, g.z, 1.0f); // rayOut[idx].resultColor, shader.comp:601
+            if (out8) out8[i] = pack_rgba8(A, g);
+        }
+    }
+    if (COUNT) flush_counts(A, cnt);
+}
+
+template <int GEOM>
+static void launch_query_g(const KArgs& A, const float4* rays, uint32_t n, uint32_t* out8, float4* out32, uint4* hits,
+                           bool count, hipStream_t stream) {
+    const dim3 grid((n + 63u) / 64u), block(64);
+    // the deferred-child capacity does not change a result, so two serve every depth (launch_trace
+    // compiles seven): 3 for max_depth <= 4, 19 beyond; COUNT launches take the deep one
+    if (!out8 && !out32)
+        hipLaunchKernelGGL((ray_query_kernel<0, false, GEOM, false>), grid, block, 0, stream, A, rays, n, out8, out32, hits);
+    else if (count)
+        hipLaunchKernelGGL((ray_query_kernel<19, true, GEOM, true>), grid, block, 0, stream, A, rays, n, out8, out32, hits);
+    else if (A.max_depth <= 4)
+        hipLaunchKernelGGL((ray_query_kernel<3, false, GEOM, true>), grid, block, 0, stream, A, rays, n, out8, out32, hits);
+    else
+        hipLaunchKernelGGL((ray_query_kernel<19, false, GEOM, true>), grid, block, 0, stream, A, rays, n, out8, out32, hits);
+}
+
+#ifndef TRT_KRES_ONLY
+hipError_t launch_ray_query(const KArgs& A0, const float4* rays, uint32_t n, uint32_t* out8, float4* out32, uint4* hits,
+                            bool count, hipStream_t stream) {
+    if (!n) return hipSuccess;
+    KArgs A = A0;
+    A.diag = nullptr;
+    // the geometry path exactly as launch_trace chooses it
+    const int geom = A.nbatch == 0 ? 0 : (A.bvh && !(A.flags & TRT_FLAG_BATCH_WALK)) ? (A.bvh_waves4 ? 3 : 2) : 1;
+    if (geom == 0) launch_query_g<0>(A, rays, n, out8, out32, hits, count, stream);
+    else if (geom == 1) launch_query_g<1>(A, rays, n, out8, out32, hits, count, stream);
+    else if (geom == 2) launch_query_g<2>(A, rays, n, out8, out32, hits, count, stream);
+    else launch_query_g<3>(A, rays, n, out8, out32, hits, count, stream);
+    return hipGetLastError();
+}
+#endif
 
 // Launch helper: picks the deferred-stack capacity from max_depth (children are made only
 // for depth+1 < max_depth, so at most max_depth-1 refraction children wait at once; inside a

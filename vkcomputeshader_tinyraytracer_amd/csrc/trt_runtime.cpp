@@ -26,6 +26,7 @@
 #include "trt_bands.h"
 #include "trt_ctx.h"
 #include "trt_device.h"
+#include "trt_qray.h"
 
 namespace trt {
 // HIP creates a stream's hardware queue at its first submission, which costs ~0.1 ms: every
@@ -39,6 +40,8 @@ hipError_t launch_trace(const KArgs& A, hipStream_t stream, bool count);
 hipError_t launch_envp(const uint32_t* env, uint2* out, uint32_t W, uint32_t H, hipStream_t stream);
 hipError_t launch_sky(const KArgs& A, uint32_t* out, hipStream_t stream);
 hipError_t launch_shadow_batch(const KArgs& A, const float4* rays, uint32_t n, uint32_t* occ, hipStream_t stream);
+hipError_t launch_ray_query(const KArgs& A, const float4* rays, uint32_t n, uint32_t* out8, float4* out32, uint4* hits,
+                            bool count, hipStream_t stream);
 uint32_t collapse_bvh4(const std::vector<BvhNode>& b2, std::vector<Bvh4Node>& b4);
 uint32_t bvh_depth(const std::vector<BvhNode>& b2);
 bool quantize_bvh4(const std::vector<Bvh4Node>& b4, std::vector<Bvh4QNode>& out);
@@ -177,6 +180,20 @@ void fill_view(KArgs& A, uint32_t f, const trt_view& v) {
     std::memcpy(A.view[f], &v, sizeof(trt_view));
 }
 
+// Steps 1 and 2 of the view contract (abi.h trt_view) for one pixel at spp 1: dir_z as fill_args
+// (main.cpp:1503); the rest is primary_dir's spp-1 arithmetic, operation for operation (this
+// file compiles with -ffp-contract=off).  Shared by trt_view_rays and trt_pixel_ray.
+float view_dz(const trt_params* p) { return (float)(-1.0 * ((double)p->height / (2.0 * std::tan((double)p->fov / 2.0)))); }
+void view_pixel_dir(const trt_params* p, const trt_view& V, float dz, uint32_t x, uint32_t y, float w[3]) {
+    const uint32_t W = p->width, H = p->height;
+    const uint32_t row = ((p->flags & TRT_FLAG_ROW_QUIRK) && x + 1u == W) ? y + 1u : y;
+    const float dx = ((float)x + 0.5f) - (float)W * 0.5f;
+    const float dy = -((float)row + 0.5f) + (float)H * 0.5f;
+    const float inv = 1.0f / std::sqrt((dx * dx + dy * dy) + dz * dz);
+    const float cx = dx * inv, cy = dy * inv, cz = dz * inv;
+    for (int a = 0; a < 3; ++a) w[a] = (cx * V.right[a] + cy * V.up[a]) + cz * V.back[a];
+}
+
 // Frames that may share a launch: every UBO field but camPos equal (byte-wise).
 bool same_but_camera(const trt_ubo& a, const trt_ubo& b) {
     constexpr size_t cam = offsetof(trt_ubo, camPos);
@@ -229,24 +246,40 @@ int trt_view_rays(const trt_params* p, const trt_view* v, trt_ray* out) {
     if (!p || !out || p->width == 0 || p->height == 0 || p->width > 65536 || p->height > 65536) return TRT_ERR_INVALID;
     const trt_view& V = v ? *v : kViewIdentity;
     const uint32_t W = p->width, H = p->height;
-    // dir_z as fill_args (main.cpp:1503); the rest is primary_dir's spp-1 arithmetic, operation
-    // for operation (this file compiles with -ffp-contract=off)
-    const float dz = (float)(-1.0 * ((double)H / (2.0 * std::tan((double)p->fov / 2.0))));
+    const float dz = view_dz(p);
     for (uint32_t y = 0; y < H; ++y) {
         for (uint32_t x = 0; x < W; ++x) {
-            const uint32_t row = ((p->flags & TRT_FLAG_ROW_QUIRK) && x + 1u == W) ? y + 1u : y;
-            const float dx = ((float)x + 0.5f) - (float)W * 0.5f;
-            const float dy = -((float)row + 0.5f) + (float)H * 0.5f;
-            const float inv = 1.0f / std::sqrt((dx * dx + dy * dy) + dz * dz);
-            const float cx = dx * inv, cy = dy * inv, cz = dz * inv;
             trt_ray& r = out[(size_t)y * W + x];
             std::memset(&r, 0, sizeof(r));
             float w[3];
-            for (int a = 0; a < 3; ++a) w[a] = (cx * V.right[a] + cy * V.up[a]) + cz * V.back[a];
+            view_pixel_dir(p, V, dz, x, y, w);
             r.dir.x = w[0];
             r.dir.y = w[1];
             r.dir.z = w[2];
             r.dir.w = 1.0f;
+        }
+    }
+    return TRT_OK;
+}
+
+int trt_pixel_ray(const trt_params* p, const trt_view* v, const float cam[3], uint32_t x, uint32_t y, trt_qray* out) {
+    if (!p || !cam || !out || p->width == 0 || p->height == 0 || p->width > 65536 || p->height > 65536) return TRT_ERR_INVALID;
+    if (x >= p->width || y >= p->height) return TRT_ERR_INVALID;
+    std::memset(out, 0, sizeof(*out));
+    view_pixel_dir(p, v ? *v : kViewIdentity, view_dz(p), x, y, out->dir);
+    for (int a = 0; a < 3; ++a) out->org[a] = cam[a];
+    return TRT_OK;
+}
+
+int trt_check_rays(const trt_qray* rays, uint32_t n, uint32_t* first_bad) {
+    if (first_bad) *first_bad = 0;
+    if (n == 0) return TRT_OK;
+    if (!rays) return TRT_ERR_INVALID;
+    for (uint32_t i = 0; i < n; ++i) {
+        const trt_qray& r = rays[i];
+        if (!trt::qray_valid(r.org[0], r.org[1], r.org[2], r.dir[0], r.dir[1], r.dir[2])) {
+            if (first_bad) *first_bad = i;
+            return TRT_ERR_INVALID;
         }
     }
     return TRT_OK;
@@ -343,6 +376,8 @@ int trt_destroy(trt_ctx* c) {
     (void)hipFree(c->d_out8);
     (void)hipFree(c->d_out32);
     (void)hipFree(c->d_rays);
+    (void)hipFree(c->d_qrays);
+    (void)hipFree(c->d_qhits);
     (void)hipFree(c->d_counters);
     for (hipEvent_t e : c->fev) (void)hipEventDestroy(e);
     for (auto& b : c->split) {
@@ -1206,6 +1241,30 @@ int fence_split(trt_ctx* c, const KArgs& A, uint32_t slot, hipStream_t stream) {
     return TRT_OK;
 }
 
+// trt_stats from the device counters, in KArgs::counters order (kernel_ms is the caller's).
+void stats_from_counters(trt_stats* st, const unsigned long long* cnt) {
+    st->primary_rays = cnt[0];
+    st->secondary_rays = cnt[1];
+    st->shadow_rays = cnt[2];
+    st->misses = cnt[3];
+    st->tri_nearest = cnt[4];
+    st->sphere_tests = cnt[5];
+    st->batch_tests = cnt[6];
+    st->batch_hits = cnt[7];
+    st->tri_tests = cnt[8];
+    st->node_tests = cnt[9];
+    st->tri_past_a = cnt[10];
+    st->tri_past_u = cnt[11];
+    st->tri_past_v = cnt[12];
+    st->shadow_skipped = cnt[13];
+    st->skipped_sphere_tests = cnt[14];
+    st->skipped_box_tests = cnt[15];
+    st->skipped_tri_tests = cnt[16];
+    st->skipped_tri_past_a = cnt[17];
+    st->skipped_tri_past_u = cnt[18];
+    st->skipped_tri_past_v = cnt[19];
+}
+
 // trt_render's split slot: one per distinct stream among the last TRT_BUILD_MAX_IN_FLIGHT
 // (so renders alternating between streams overlap), reused least recently first.
 uint32_t render_slot(trt_ctx* c, hipStream_t s) {
@@ -1507,27 +1566,100 @@ int trt_render(trt_ctx* c, const trt_params* p, uint8_t* out8, float* out32, trt
         HIP_TRY(c, hipMemcpyAsync(cnt, c->d_counters, sizeof(cnt), hipMemcpyDeviceToHost, c->stream));
     if (!dev || count || timing) HIP_TRY(c, hipStreamSynchronize(c->stream));
     if (st) {
-        st->primary_rays = cnt[0];
-        st->secondary_rays = cnt[1];
-        st->shadow_rays = cnt[2];
-        st->misses = cnt[3];
-        st->tri_nearest = cnt[4];
-        st->sphere_tests = cnt[5];
-        st->batch_tests = cnt[6];
-        st->batch_hits = cnt[7];
-        st->tri_tests = cnt[8];
-        st->node_tests = cnt[9];
-        st->tri_past_a = cnt[10];
-        st->tri_past_u = cnt[11];
-        st->tri_past_v = cnt[12];
-        st->shadow_skipped = cnt[13];
-        st->skipped_sphere_tests = cnt[14];
-        st->skipped_box_tests = cnt[15];
-        st->skipped_tri_tests = cnt[16];
-        st->skipped_tri_past_a = cnt[17];
-        st->skipped_tri_past_u = cnt[18];
-        st->skipped_tri_past_v = cnt[19];
+        stats_from_counters(st, cnt);
         st->kernel_ms = 0.0;
+        if (timing) {
+            float ms = 0.0f;
+            HIP_TRY(c, hipEventElapsedTime(&ms, c->ev0, c->ev1));
+            st->kernel_ms = ms;
+        }
+    }
+    return TRT_OK;
+}
+
+// Ray queries (abi.h): the caller's rays through ray_query_kernel.  Nothing of the context that a
+// frame depends on is written: the launch reads the scene bindings and the UBO's spheres and
+// lights through fill_args and takes no sky table, spans, masks, view or frame slot.
+int trt_trace_rays(trt_ctx* c, const trt_params* p, const trt_qray* rays, uint32_t nrays, uint8_t* out8, float* out32,
+                   trt_qhit* hits, trt_stats* st) {
+    if (!c) return TRT_ERR_INVALID;
+    if (!p) return fail(c, TRT_ERR_INVALID, "trt_trace_rays: null params");
+    if (!c->have_scene) return fail(c, TRT_ERR_NOSCENE, "trt_trace_rays: no scene uploaded");
+    if (p->max_depth < 1 || p->max_depth > TRT_MAX_DEPTH_LIMIT)
+        return fail(c, TRT_ERR_INVALID, "trt_trace_rays: max_depth must be 1..20");
+    if (!out8 && !out32 && !hits) return fail(c, TRT_ERR_INVALID, "trt_trace_rays: no output requested");
+    const bool shade = out8 || out32;
+    if ((p->flags & TRT_FLAG_COUNT) && !shade)
+        return fail(c, TRT_ERR_INVALID, "trt_trace_rays: TRT_FLAG_COUNT needs a colour output");
+    if ((p->flags & TRT_FLAG_ENVMAP) && !c->d_env)
+        return fail(c, TRT_ERR_INVALID, "trt_trace_rays: TRT_FLAG_ENVMAP without an uploaded envmap");
+    if (nrays > TRT_QRAY_MAX_RAYS) return fail(c, TRT_ERR_INVALID, "trt_trace_rays: more than 2^28 rays");
+    if (nrays && !rays) return fail(c, TRT_ERR_INVALID, "trt_trace_rays: null rays");
+    const bool dev = (p->flags & TRT_FLAG_DEVICE_PTRS) != 0;
+    // the kernel moves a ray, a hit and a rayOut entry as 16-byte vectors, straight from and to the
+    // caller's device arrays (host arrays are staged)
+    if (dev && ((reinterpret_cast<uintptr_t>(rays) | reinterpret_cast<uintptr_t>(hits) |
+                 reinterpret_cast<uintptr_t>(out32)) & 15u))
+        return fail(c, TRT_ERR_INVALID, "trt_trace_rays: device rays, hits and out_rgba32f must be 16-byte aligned");
+    if (dev && (reinterpret_cast<uintptr_t>(out8) & 3u))
+        return fail(c, TRT_ERR_INVALID, "trt_trace_rays: device out_rgba8 must be 4-byte aligned");
+    const bool count = (p->flags & TRT_FLAG_COUNT) != 0 && st;
+    const bool timing = (p->flags & TRT_FLAG_TIMING) != 0 && st;
+    if (st) std::memset(st, 0, sizeof(*st));
+    if (nrays == 0) return TRT_OK;
+    if (!dev) { // a device array cannot be read here: the kernel applies the same predicate
+        uint32_t bad = 0;
+        if (trt_check_rays(rays, nrays, &bad) != TRT_OK)
+            return fail(c, TRT_ERR_INVALID, "trt_trace_rays: ray " + std::to_string(bad) +
+                                                " is not valid (non-finite, or direction length out of range)");
+    }
+    HIP_TRY(c, hipSetDevice(c->device));
+
+    // what the query reads of p, in a frame-shaped trt_params for fill_args: one row of 64 pixels
+    // stands in for the image (no field of it reaches the kernel)
+    trt_params q;
+    trt_params_default(&q);
+    q.width = 64;
+    q.height = 1;
+    q.max_depth = p->max_depth;
+    q.flags = p->flags & (TRT_FLAG_SPHERES | TRT_FLAG_FLOOR | TRT_FLAG_CHECKER | TRT_FLAG_ENVMAP | TRT_FLAG_BATCH_WALK |
+                          TRT_FLAG_SRGB_OUT | TRT_FLAG_DEVICE_PTRS | TRT_FLAG_COUNT | TRT_FLAG_TIMING);
+    int rc;
+    if ((rc = ensure_envp(c, &q, c->stream)) != TRT_OK) return rc;
+    KArgs A;
+    fill_args(c, &q, A);
+    A.view_on = 0; // the rays are the caller's
+
+    const float4* d_rays = reinterpret_cast<const float4*>(rays);
+    uint32_t* d8 = reinterpret_cast<uint32_t*>(out8);
+    float4* d32 = reinterpret_cast<float4*>(out32);
+    uint4* dh = reinterpret_cast<uint4*>(hits);
+    const size_t n = nrays;
+    if (!dev) {
+        if ((rc = ensure(c, &c->d_qrays, &c->capqrays, n * sizeof(trt_qray), "alloc query rays")) != TRT_OK) return rc;
+        if (out8 && (rc = ensure(c, &c->d_out8, &c->cap8, n * 4, "alloc rgba8")) != TRT_OK) return rc;
+        if (out32 && (rc = ensure(c, &c->d_out32, &c->cap32, n * 16, "alloc rgba32f")) != TRT_OK) return rc;
+        if (hits && (rc = ensure(c, &c->d_qhits, &c->capqhits, n * sizeof(trt_qhit), "alloc query hits")) != TRT_OK) return rc;
+        HIP_TRY(c, hipMemcpyAsync(c->d_qrays, rays, n * sizeof(trt_qray), hipMemcpyHostToDevice, c->stream));
+        d_rays = static_cast<const float4*>(c->d_qrays);
+        d8 = out8 ? static_cast<uint32_t*>(c->d_out8) : nullptr;
+        d32 = out32 ? static_cast<float4*>(c->d_out32) : nullptr;
+        dh = hits ? static_cast<uint4*>(c->d_qhits) : nullptr;
+    }
+    if (count) HIP_TRY(c, hipMemsetAsync(c->d_counters, 0, 32 * sizeof(unsigned long long), c->stream));
+    if (timing) HIP_TRY(c, hipEventRecord(c->ev0, c->stream));
+    HIP_TRY(c, trt::launch_ray_query(A, d_rays, nrays, d8, d32, dh, count, c->stream));
+    if (timing) HIP_TRY(c, hipEventRecord(c->ev1, c->stream));
+    if (!dev) {
+        if (out8) HIP_TRY(c, hipMemcpyAsync(out8, c->d_out8, n * 4, hipMemcpyDeviceToHost, c->stream));
+        if (out32) HIP_TRY(c, hipMemcpyAsync(out32, c->d_out32, n * 16, hipMemcpyDeviceToHost, c->stream));
+        if (hits) HIP_TRY(c, hipMemcpyAsync(hits, c->d_qhits, n * sizeof(trt_qhit), hipMemcpyDeviceToHost, c->stream));
+    }
+    unsigned long long cnt[32] = {0};
+    if (count) HIP_TRY(c, hipMemcpyAsync(cnt, c->d_counters, sizeof(cnt), hipMemcpyDeviceToHost, c->stream));
+    if (!dev || count || timing) HIP_TRY(c, hipStreamSynchronize(c->stream));
+    if (st) {
+        stats_from_counters(st, cnt);
         if (timing) {
             float ms = 0.0f;
             HIP_TRY(c, hipEventElapsedTime(&ms, c->ev0, c->ev1));

@@ -33,6 +33,9 @@ class Renderer:
         self._h = h
         self.device = device
         self.scene: Scene | None = None
+        # the camera position and the view in force, for pixel_ray / pick
+        self._cam = np.zeros(3, np.float32)
+        self._view: np.ndarray | None = None
 
     # -- errors ----------------------------------------------------------------------------
     def _check(self, rc: int):
@@ -51,10 +54,18 @@ class Renderer:
             env.ctypes.data if env is not None else None,
             0 if env is None else env.shape[1], 0 if env is None else env.shape[0]))
         self.scene = scene
+        self._cam = np.array(ubo["camPos"], np.float32).reshape(-1)[:3]
 
     def update_ubo(self, ubo: np.ndarray) -> None:
         u = np.ascontiguousarray(ubo)
         self._check(self._L.trt_update_ubo(self._h, u.ctypes.data))
+        self._cam = np.array(u["camPos"], np.float32).reshape(-1)[:3]
+
+    def _walked(self, ubos, nframes: int) -> None:
+        # a frame loop leaves the context's UBO at its last frame's (trt_render_frames): keep the
+        # camera pixel_ray / pick read in step with it
+        if ubos is not None and nframes > 0:
+            self._cam = np.array(ubos[nframes - 1]["camPos"], np.float32).reshape(-1)[:3]
 
     def set_view(self, view) -> None:
         """The context's view (trt_set_view): a T.VIEW record (scene.view_look / view_ypr), or None
@@ -62,9 +73,11 @@ class Renderer:
         a view of its own is generated in this basis; rays_in, where given, wins."""
         if view is None:
             self._check(self._L.trt_set_view(self._h, None))
+            self._view = None
             return
         v = np.ascontiguousarray(view, T.VIEW)
         self._check(self._L.trt_set_view(self._h, v.ctypes.data))
+        self._view = v.copy()
 
     @staticmethod
     def _views(views, nframes: int):
@@ -166,6 +179,97 @@ class Renderer:
         self._check(self._L.trt_render(self._h, ctypes.byref(p), o8, o32, ctypes.byref(st)))
         return out8, out32, st.as_dict()
 
+    # -- ray queries -------------------------------------------------------------------------
+    def trace_rays(self, rays, params: T.Params, *, count: bool = False, want8: bool = True, want32: bool = False,
+                   want_hits: bool = False, timing: bool = False, out8=None, out32=None, hits=None,
+                   nrays: int | None = None):
+        """Traces the caller's rays (trt_trace_rays): `rays` is a numpy array of T.QRAY (host,
+        synchronous, every ray validated first) or a torch CUDA tensor holding such records
+        (device pointers, only enqueued on the context's stream unless count / timing; a ray that
+        is not valid gets word 0, float4 0 and kind T.HIT_BAD_RAY).  Of `params` only max_depth
+        and the scene flags are read.  Outputs are made on the side of the rays unless given
+        (numpy arrays, or torch CUDA tensors with device rays; they may be longer than the query):
+        rgba8 (n, 4) uint8, rgba32f (n, 4) float32, hits (n,) T.QHIT — on the device an (n, 32)
+        uint8 tensor of the same bytes; device rays, hits and rgba32f must be 16-byte aligned (torch's
+        own allocations are; an offset view may not be: TrtError).  `nrays` limits the query to the
+        first rays.
+        Returns (rgba8, rgba32f, hits, stats_dict)."""
+        p = T.Params.from_buffer_copy(params)
+        p.rays_in = None
+        dev = _is_torch_cuda(rays)
+        if dev:
+            import torch
+
+            if not rays.is_contiguous():
+                raise ValueError("rays must be a contiguous device tensor of T.QRAY records")
+            have = rays.numel() * rays.element_size() // T.QRAY.itemsize
+            n = have if nrays is None else int(nrays)
+            if n > have:
+                raise ValueError(f"{n} rays asked of a tensor that holds {have}")
+            p.flags |= T.FLAG_DEVICE_PTRS
+
+            def made(x, want, shape, dtype, words):
+                if x is None and want:
+                    x = torch.empty(shape, dtype=dtype, device=rays.device)
+                if x is not None and not (_is_torch_cuda(x) and x.is_contiguous() and x.numel() * x.element_size() >= n * words):
+                    raise ValueError("outputs of a device query are contiguous device tensors that hold every ray")
+                return x
+
+            out8 = made(out8, want8, (n, 4), torch.uint8, 4)
+            out32 = made(out32, want32, (n, 4), torch.float32, 16)
+            hits = made(hits, want_hits, (n, T.QHIT.itemsize), torch.uint8, T.QHIT.itemsize)
+            ptrs = [rays.data_ptr()] + [x.data_ptr() if x is not None else None for x in (out8, out32, hits)]
+        else:
+            p.flags &= ~T.FLAG_DEVICE_PTRS
+            r = None if rays is None else np.ascontiguousarray(rays, T.QRAY).reshape(-1)
+            n = (0 if r is None else r.shape[0]) if nrays is None else int(nrays)
+            if r is not None and n > r.shape[0]:
+                raise ValueError(f"{n} rays asked of an array that holds {r.shape[0]}")
+
+            def made(x, want, shape, dtype):
+                if x is None and want:
+                    x = np.empty(shape, dtype)
+                if x is not None and not (isinstance(x, np.ndarray) and x.flags["C_CONTIGUOUS"] and x.dtype == dtype
+                                          and x.size >= int(np.prod(shape))):
+                    raise ValueError("outputs of a host query are C-contiguous numpy arrays that hold every ray")
+                return x
+
+            out8 = made(out8, want8, (n, 4), np.uint8)
+            out32 = made(out32, want32, (n, 4), np.float32)
+            hits = made(hits, want_hits, (n,), T.QHIT)
+            ptrs = [None if r is None else r.ctypes.data] + [x.ctypes.data if x is not None else None
+                                                              for x in (out8, out32, hits)]
+        if count:
+            p.flags |= T.FLAG_COUNT
+        else:
+            p.flags &= ~T.FLAG_COUNT
+        if timing:
+            p.flags |= T.FLAG_TIMING
+        else:
+            p.flags &= ~T.FLAG_TIMING
+        st = T.Stats()
+        self._check(self._L.trt_trace_rays(self._h, ctypes.byref(p), ptrs[0], n, ptrs[1], ptrs[2], ptrs[3],
+                                           ctypes.byref(st)))
+        return out8, out32, hits, st.as_dict()
+
+    def pixel_ray(self, params: T.Params, x: int, y: int) -> np.ndarray:
+        """The T.QRAY of pixel (x, y)'s primary ray at spp 1 under the context's current UBO
+        (camPos) and view (trt_pixel_ray)."""
+        p = T.Params.from_buffer_copy(params)
+        out = np.zeros(1, T.QRAY)
+        cam = (ctypes.c_float * 3)(*[float(v) for v in self._cam])
+        v = self._view
+        rc = self._L.trt_pixel_ray(ctypes.byref(p), None if v is None else v.ctypes.data, cam, int(x), int(y),
+                                   out.ctypes.data)
+        if rc != 0:
+            raise TrtError(rc, f"trt_pixel_ray: pixel ({x}, {y}) is outside the {p.width}x{p.height} image")
+        return out
+
+    def pick(self, params: T.Params, x: int, y: int) -> np.ndarray:
+        """What is under pixel (x, y): the T.QHIT record of that pixel's primary ray under the
+        context's current UBO and view — one trt_pixel_ray and a one-ray hits-only query."""
+        return self.trace_rays(self.pixel_ray(params, x, y), params, want8=False, want_hits=True)[2][0]
+
     def render_frames(self, params: T.Params, out8, nframes: int, ubos: np.ndarray | None = None,
                       frame_stride: int = 0, timing: bool = False, time_every: int = 1, views=None) -> int:
         """Native frame loop (trt_render_frames): `nframes` frames enqueued on the context's
@@ -201,6 +305,7 @@ class Renderer:
         else:
             self._check(self._L.trt_render_frames_view(self._h, ctypes.byref(p), up, v.ctypes.data, nframes,
                                                        out8.data_ptr(), frame_stride, time_every))
+        self._walked(u, nframes)
         return int(self._L.trt_timed_launches(self._h, None, 0)) if timing else 0
 
     def frames_call(self, params: T.Params, out8, nframes: int, ubos: np.ndarray | None = None,
@@ -234,6 +339,7 @@ class Renderer:
                 rc = fnv(h, pp, up, vp, nframes, op, frame_stride, 0)
                 if rc:
                     self._check(rc)
+                self._walked(u, nframes)
             call.keep = keep
             return call
 
@@ -241,6 +347,7 @@ class Renderer:
             rc = fn(h, pp, up, nframes, op, frame_stride, 0)
             if rc:
                 self._check(rc)
+            self._walked(u, nframes)
         call.keep = keep
         return call
 

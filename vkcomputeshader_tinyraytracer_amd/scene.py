@@ -159,6 +159,33 @@ def view_rays(params: T.Params, view=None) -> np.ndarray:
     return out
 
 
+def pinhole_qrays(params: T.Params, view=None, cam=(0.0, 0.0, 0.0)) -> np.ndarray:
+    """view_rays plus an origin: the (height, width) T.QRAY records of the pinhole camera at `cam`
+    under `view`, for Renderer.trace_rays — the rays a frame of that view and camPos traces."""
+    r = view_rays(params, view)
+    q = np.zeros(r.shape, T.QRAY)
+    q["dir"] = r["dir"][..., :3]
+    q["org"] = np.asarray(cam, np.float32)
+    return q
+
+
+def equirect_qrays(width: int, height: int, cam=(0.0, 0.0, 0.0)) -> np.ndarray:
+    """A 360-degree panorama camera at `cam`: (height, width) T.QRAY records whose directions go
+    through the centres of the texels of a width x height equirectangular image — the inverse of
+    the shader's direction_to_uv (shader.comp:410-416: u = (atan(z, x) + pi) / 2 pi, v = acos(y) /
+    pi), computed in float64 and rounded once to float32 (the kernel normalizes)."""
+    u = (np.arange(width, dtype=np.float64) + 0.5) / width
+    v = (np.arange(height, dtype=np.float64) + 0.5) / height
+    theta = (u * 2.0 * np.pi - np.pi)[None, :]
+    phi = (v * np.pi)[:, None]
+    q = np.zeros((height, width), T.QRAY)
+    q["dir"][..., 0] = np.sin(phi) * np.cos(theta)
+    q["dir"][..., 1] = np.cos(phi) * np.ones_like(theta)
+    q["dir"][..., 2] = np.sin(phi) * np.sin(theta)
+    q["org"] = np.asarray(cam, np.float32)
+    return q
+
+
 def camera_orbit(ubo: np.ndarray, n: int, speed: float = 0.02, yaw_step: float = 1.0, pitch_step: float = -0.25,
                  yaw0: float = 0.0, pitch0: float = 0.0) -> tuple[np.ndarray, np.ndarray]:
     """camera_path with a camera that turns while it walks (mouse look held with W and D): n

@@ -47,7 +47,19 @@ RAY = np.dtype([("dir", *F4), ("resultColor", *F4)])
 VIEW = np.dtype([("right", "<f4", (3,)), ("up", "<f4", (3,)), ("back", "<f4", (3,))])
 MAX_VIEW_FRAMES = 32  # TRT_MAX_VIEW_FRAMES: frames of a launch with an oriented frame
 
-assert VIEW.itemsize == 36
+# trt_qray / trt_qhit (abi.h): one ray of a query (Renderer.trace_rays) and its nearest hit
+QRAY = np.dtype([("org", "<f4", (3,)), ("pad0", "<f4"), ("dir", "<f4", (3,)), ("pad1", "<f4")])
+QHIT = np.dtype([("t", "<f4"), ("kind", "<u4"), ("index", "<u4"), ("u", "<f4"), ("v", "<f4"), ("n", "<f4", (3,))])
+HIT_NONE = 0  # t = 1e10, the rest 0
+HIT_FLOOR = 1
+HIT_SPHERE = 2  # index 0..3
+HIT_TRIANGLE = 3  # index into the scene's triangle array; u, v weigh v1, v2
+HIT_BAD_RAY = 0xFFFFFFFF  # a device-pointer query's record of a ray that is not valid
+QRAY_MIN_LEN2 = np.float32(1e-30)  # TRT_QRAY_MIN_LEN2 / MAX_LEN2: bounds of the direction's squared length
+QRAY_MAX_LEN2 = np.float32(1e30)
+QRAY_MAX_RAYS = 1 << 28
+
+assert VIEW.itemsize == 36 and QRAY.itemsize == 32 and QHIT.itemsize == 32
 assert MATERIAL.itemsize == 48 and SPHERE.itemsize == 64
 assert TRIANGLE.itemsize == 144 and MODEL.itemsize == 96
 assert UBO.itemsize == 352 and RAY.itemsize == 32
