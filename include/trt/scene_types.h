@@ -30,7 +30,11 @@ typedef struct trt_vec4 { float x, y, z, w; } trt_vec4;
 typedef struct trt_ivec4 { int32_t x, y, z, w; } trt_ivec4;
 
 /* albedo = (diffuse weight, specular weight, reflection weight, refraction weight);
- * diffuse_specular = (kd.rgb, specular exponent); refractive.x = index of refraction. */
+ * diffuse_specular = (kd.rgb, specular exponent); refractive.x = index of refraction.
+ * Domain: the specular exponent is > 0 (the tests draw it from [1, 1425]).  The kernel raises
+ * max(0, dot(reflect_dir, view)) to it as exp2(y * log2(x)), which is written for y > 0; at
+ * y = 0 the base may be 0, GLSL leaves pow(0, 0) undefined and libm answers 1, so such a
+ * material has no defined picture. */
 typedef struct trt_material {
     trt_vec4 albedo;
     trt_vec4 diffuse_specular;

@@ -7,6 +7,8 @@ import ctypes
 
 import numpy as np
 
+from oracle import oracle as orc
+from tests.sky_spans_common import assert_inside, at, background
 from vkcomputeshader_tinyraytracer_amd import types as T
 from vkcomputeshader_tinyraytracer_amd._lib import lib
 
@@ -66,3 +68,20 @@ def floor_tiles(span: np.ndarray, sph: np.ndarray) -> int:
 
 def floor_share(span: np.ndarray, sph: np.ndarray, width: int) -> float:
     return floor_tiles(span, sph) / (span.shape[0] * span.shape[1] * ((width + 7) // 8))
+
+
+def sphere_hits(sc, ubo, flags=None, **params):
+    """Per-pixel mask of the primary rays that hit a sphere with the floor out of the way (every
+    ray that passes sphere_hit, also one whose floor hit is nearer): the oracle's depth-1 frame
+    without envmap and floor, compared with the constant background.  Spheres off: none.
+    `params`: further settings of the frame (fov)."""
+    fl = sc.flags if flags is None else flags
+    if not (fl & T.FLAG_SPHERES):
+        return np.zeros((sc.height, sc.width), bool)
+    a = at(sc, ubo)
+    m8 = orc.render(a, a.params(max_depth=1, flags=fl & ~T.FLAG_ENVMAP & ~T.FLAG_FLOOR, **params))[0]
+    return ~(m8 == background()).all(axis=-1)
+
+
+def assert_inside_interval(hits, sph, rows=None):
+    assert_inside(hits, sph, rows, what="sphere pixels outside their interval")

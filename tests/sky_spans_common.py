@@ -7,6 +7,7 @@ import ctypes
 
 import numpy as np
 
+from oracle import oracle as orc
 from vkcomputeshader_tinyraytracer_amd import scene as S, types as T
 from vkcomputeshader_tinyraytracer_amd._lib import lib
 
@@ -80,3 +81,34 @@ def culled_share(span: np.ndarray, width: int) -> float:
     """Share of the launch's tile-frames outside the spans."""
     ntx = (width + 7) // 8
     return 1.0 - float((span[..., 1] - span[..., 0]).sum()) / (span.shape[0] * span.shape[1] * ntx)
+
+
+_BG: dict = {}
+
+
+def background() -> np.ndarray:
+    """The RGBA8 the oracle writes for a primary miss with the envmap off."""
+    if "bg" not in _BG:
+        small = S.config_c2(16, 8, env_size=(64, 32))
+        _BG["bg"] = orc.render(small, small.params(max_depth=1, flags=T.FLAG_ROW_QUIRK))[0][0, 0]
+    return _BG["bg"]
+
+
+def hits(sc, ubo, flags=None, **params):
+    """Per-pixel primary hit mask as tests/test_gpu_sky_table.py::_oracle derives it: the oracle's
+    depth-1 frame with the envmap off, compared with the constant background.  `params`: further
+    settings of the frame (fov)."""
+    a = at(sc, ubo)
+    fl = (sc.flags if flags is None else flags) & ~T.FLAG_ENVMAP
+    m8 = orc.render(a, a.params(max_depth=1, flags=fl, **params))[0]
+    return ~(m8 == background()).all(axis=-1)
+
+
+def assert_inside(hits, span, rows=None, what="hit pixels outside their span"):
+    """Every hit pixel of frame rows `rows` (all, or a band group's) lies inside its row's span."""
+    if rows is not None:
+        hits = hits[rows]
+    ys, xs = np.nonzero(hits)
+    c0, c1 = span[ys // 8, 0], span[ys // 8, 1]
+    bad = (xs // 8 < c0) | (xs // 8 >= c1)
+    assert not bad.any(), f"{int(bad.sum())} {what}, first at compact row {ys[bad][0]}, x {xs[bad][0]}"

@@ -8,38 +8,15 @@ from __future__ import annotations
 import numpy as np
 import pytest
 
-from oracle import oracle as orc
-from tests.sky_spans_common import ADVERSARIAL, MUST_BE_FULL, at, culled_share, is_full, spans, ubos_at
+from tests.sky_spans_common import (ADVERSARIAL, MUST_BE_FULL, assert_inside as _assert_inside, culled_share, hits as _hits,
+                                    is_full, spans, ubos_at)
 from vkcomputeshader_tinyraytracer_amd import scene as S, types as T
 
 ENV = (64, 32)
-_BG: dict = {}
 
 
 def _scene(w, h):
     return S.config_c2(w, h, env_size=ENV)
-
-
-def _hits(sc, ubo, flags=None):
-    """Per-pixel primary hit mask as tests/test_gpu_sky_table.py::_oracle derives it: the oracle's
-    depth-1 frame with the envmap off, compared with the constant background."""
-    a = at(sc, ubo)
-    fl = (sc.flags if flags is None else flags) & ~T.FLAG_ENVMAP
-    m8 = orc.render(a, a.params(max_depth=1, flags=fl))[0]
-    if "bg" not in _BG:
-        small = _scene(16, 8)
-        _BG["bg"] = orc.render(small, small.params(max_depth=1, flags=T.FLAG_ROW_QUIRK))[0][0, 0]
-    return ~(m8 == _BG["bg"]).all(axis=-1)
-
-
-def _assert_inside(hits, span, rows=None):
-    """Every hit pixel of frame rows `rows` (all, or a band group's) lies inside its row's span."""
-    if rows is not None:
-        hits = hits[rows]
-    ys, xs = np.nonzero(hits)
-    c0, c1 = span[ys // 8, 0], span[ys // 8, 1]
-    bad = (xs // 8 < c0) | (xs // 8 >= c1)
-    assert not bad.any(), f"{int(bad.sum())} hit pixels outside their span, first at compact row {ys[bad][0]}, x {xs[bad][0]}"
 
 
 @pytest.mark.parametrize("w,h", [(128, 96), (100, 52)])

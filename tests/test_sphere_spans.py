@@ -13,42 +13,17 @@ from pathlib import Path
 import numpy as np
 import pytest
 
-from oracle import oracle as orc
-from tests.floor_class_common import floor_share, intervals, raw_words
-from tests.sky_spans_common import ADVERSARIAL, MUST_BE_FULL, NON_FINITE, at, ubos_at
+from tests.floor_class_common import assert_inside_interval as _assert_inside, floor_share, intervals, raw_words
+from tests.floor_class_common import sphere_hits as _sphere_hits
+from tests.sky_spans_common import ADVERSARIAL, MUST_BE_FULL, NON_FINITE, ubos_at
 from vkcomputeshader_tinyraytracer_amd import scene as S, types as T
 
 ENV = (64, 32)
 GOLDEN = Path(__file__).resolve().parent / "golden" / "sky_spans_parent.npz"
-_BG: dict = {}
 
 
 def _scene(w, h):
     return S.config_c2(w, h, env_size=ENV)
-
-
-def _sphere_hits(sc, ubo, flags=None):
-    """Per-pixel mask of the primary rays that hit a sphere with the floor out of the way (every
-    ray that passes sphere_hit, also one whose floor hit is nearer): the oracle's depth-1 frame
-    without envmap and floor, compared with the constant background.  Spheres off: none."""
-    fl = sc.flags if flags is None else flags
-    if not (fl & T.FLAG_SPHERES):
-        return np.zeros((sc.height, sc.width), bool)
-    a = at(sc, ubo)
-    m8 = orc.render(a, a.params(max_depth=1, flags=fl & ~T.FLAG_ENVMAP & ~T.FLAG_FLOOR))[0]
-    if "bg" not in _BG:
-        small = _scene(16, 8)
-        _BG["bg"] = orc.render(small, small.params(max_depth=1, flags=T.FLAG_ROW_QUIRK))[0][0, 0]
-    return ~(m8 == _BG["bg"]).all(axis=-1)
-
-
-def _assert_inside(hits, sph, rows=None):
-    if rows is not None:
-        hits = hits[rows]
-    ys, xs = np.nonzero(hits)
-    s0, s1 = sph[ys // 8, 0], sph[ys // 8, 1]
-    bad = (xs // 8 < s0) | (xs // 8 >= s1)
-    assert not bad.any(), f"{int(bad.sum())} sphere pixels outside their interval, first at compact row {ys[bad][0]}, x {xs[bad][0]}"
 
 
 def _full(a, width):
