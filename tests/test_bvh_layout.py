@@ -74,6 +74,12 @@ def test_every_triangle_point_is_inside_a_leaf_path(name, golden_meshes):
         sc = S.config_readme(golden_meshes, env_size=(64, 32))
     else:
         sc = S.CONFIGS[name](64, 48, env_size=(64, 32))
+    assert_every_triangle_point_is_inside_a_leaf_path(sc)
+
+
+def assert_every_triangle_point_is_inside_a_leaf_path(sc):
+    """The check of test_every_triangle_point_is_inside_a_leaf_path on any Scene (also run on the
+    adversarial meshes by tests/test_mesh_cases.py)."""
     nodes, refs = _export(sc)
     boxes = nodes[:, :12].view(np.float32).reshape(-1, 4, 3)  # lo0, hi0, lo1, hi1
     child = nodes[:, 12:14]
@@ -138,7 +144,9 @@ def test_bvh_depth_is_bounded(base, n):
     """Advisor round 5 (high): binned SAH splits past kBvhSahDepth could peel a few primitives
     per level (geometrically spaced centroids put all but the largest in the first bin), so the
     BVH2 depth was unbounded while the BVH2 walk's stack holds kBvhStack = 64 entries — and these
-    scenes' BVH4 needs a stack deeper than 64 (out[4]), so the runtime does fall back to that walk.
+    scenes' BVH4 needs a stack deeper than 64 (out[4]), so the runtime does fall back to that walk
+    (rendered on the GPU by tests/test_gpu_mesh_cases.py::test_fallback_walk_first: strip_b12 is
+    the (1.2, 400) strip here, built through the scene builder so that its batches have boxes).
     The build now switches to median splits below that depth: depth <= 32 + log2(n) + 1."""
     xs = [base ** k for k in range(n)] if base else list(np.linspace(-5.0, 5.0, n))
     tris, models = _strip_scene(xs)

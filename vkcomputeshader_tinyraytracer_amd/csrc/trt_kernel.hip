@@ -683,6 +683,33 @@ __device__ __forceinline__ bool visit4(f3 o, f3 inv, float best, const float4& l
 #ifndef TRT_BVH_QUANT
 #define TRT_BVH_QUANT 1
 #endif
+// The origin term A of a quantized axis (plane distance = A + q * B, A = (p - o) * inv).  For an
+// axis-parallel ray inv is 1e30 (cull_inv), and a node origin more than 3.4e8 from the ray's then
+// overflows A to an infinity while B stays finite: near and far plane land on the same infinity,
+// `tf > eps` fails, and a child that the float boxes enter (their two products overflow to
+// opposite infinities) is culled with the triangles the reference hits in it.  An infinite A
+// becomes NaN here, so the NaN-ignoring min / max leave that axis unconstrained, like every other
+// degenerate slab: fma(a, 0, a) is a, bit for bit, for a finite a (a * 0 is a zero of a's sign)
+// and NaN for an infinite one.  One VALU per axis and visit.
+__device__ __forceinline__ float quant_origin_term(float a) { return __builtin_fmaf(a, 0.0f, a); }
+// The wave-coherent shadow walk (shadow_wave_q) computes the same terms without that guard: it is
+// taken only for queries none of whose origin terms can overflow at any node.  Every node's grid
+// origin lies within [p - s, p + 256 s] of the root's grid (origin p, step s: child boxes nest and
+// steps shrink), and the walking lanes' origins within TRT_SHADOW_WAVE_EXT of the first one's, f.
+// With |p| <= 1e17, s <= 2^48 and |f| <= 1e17 (wave-uniform: compared as integers, the bit
+// patterns of non-negative floats order like their values, NaN and inf above every bound) and
+// |inv| <= 1e20 per lane, |p_node - o| * |inv| < 3e17 * 1e20.
+__device__ __forceinline__ bool quant_terms_finite(const KArgs& A, float fx, float fy, float fz, f3 inv) {
+    typedef __attribute__((address_space(4))) const uint32_t cuint;
+    const cuint* R = (const cuint*)(A.bvh4q);
+    constexpr uint32_t kAbs = 0x7fffffffu, k1e17 = 0x5bb1a2bcu; // 1e17f
+    const uint32_t ex = R[3];
+    const bool uniform_ok = (R[0] & kAbs) <= k1e17 && (R[1] & kAbs) <= k1e17 && (R[2] & kAbs) <= k1e17 &&
+                            (ex & 0xffu) <= 127u + 48u && ((ex >> 8) & 0xffu) <= 127u + 48u &&
+                            ((ex >> 16) & 0xffu) <= 127u + 48u && (__float_as_uint(fx) & kAbs) <= k1e17 &&
+                            (__float_as_uint(fy) & kAbs) <= k1e17 && (__float_as_uint(fz) & kAbs) <= k1e17;
+    return uniform_ok && fmaxf(fmaxf(fabsf(inv.x), fabsf(inv.y)), fabsf(inv.z)) <= 1e20f;
+}
 template <bool COUNT, typename Stack>
 __device__ __forceinline__ bool visit4q(f3 o, f3 inv, float best, const float4& pe, const uint4& qa,
                                         const uint4& qb, const uint4& ch, Stack& stack, uint32_t& node, Cnt& c) {
@@ -690,9 +717,10 @@ __device__ __forceinline__ bool visit4q(f3 o, f3 inv, float best, const float4& 
     const float sx = __uint_as_float((ex & 0xffu) << 23);
     const float sy = __uint_as_float(((ex >> 8) & 0xffu) << 23);
     const float sz = __uint_as_float(((ex >> 16) & 0xffu) << 23);
-    const float ax = (pe.x - o.x) * inv.x, bx = sx * inv.x;
-    const float ay = (pe.y - o.y) * inv.y, by = sy * inv.y;
-    const float az = (pe.z - o.z) * inv.z, bz = sz * inv.z;
+    // quant_origin_term: an origin term that overflowed must not put the axis' far plane at -inf
+    const float ax = quant_origin_term((pe.x - o.x) * inv.x), bx = sx * inv.x;
+    const float ay = quant_origin_term((pe.y - o.y) * inv.y), by = sy * inv.y;
+    const float az = quant_origin_term((pe.z - o.z) * inv.z), bz = sz * inv.z;
     // qa = (qlo.x, qlo.y, qlo.z, qhi.x), qb = (qhi.y, qhi.z, -, -)
     const uint32_t nx = inv.x >= 0.0f ? qa.x : qa.w, fx = inv.x >= 0.0f ? qa.w : qa.x;
     const uint32_t ny = inv.y >= 0.0f ? qa.y : qb.x, fy = inv.y >= 0.0f ? qb.x : qa.y;
@@ -1102,7 +1130,7 @@ __device__ __forceinline__ bool shadow_intersect(const KArgs& A, f3 o, f3 d, flo
                 const float fy = __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(o.y)));
                 const float fz = __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(o.z)));
                 const float e = fmaxf(fmaxf(fabsf(o.x - fx), fabsf(o.y - fy)), fabsf(o.z - fz));
-                const bool near = e <= (float)TRT_SHADOW_WAVE_EXT;
+                const bool near = e <= (float)TRT_SHADOW_WAVE_EXT && quant_terms_finite(A, fx, fy, fz, inv);
                 const uint64_t nm = __ballot(near);
                 if (nm == __ballot(true)) return shadow_wave_q(A, o, d, inv, max_dist, slab);
             }

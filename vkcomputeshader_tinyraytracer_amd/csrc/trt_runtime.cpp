@@ -534,9 +534,15 @@ int trt_upload_scene(trt_ctx* c, const trt_ubo* ubo, const trt_triangle* tris, u
                 float4 a = make_float4(inf, inf, inf, 0.0f), z = make_float4(-inf, -inf, -inf, 0.0f);
                 bool bad = false;
                 for (size_t j = 8 * k; j < std::min(prev_lo.size(), 8 * k + 8); ++j) {
-                    const float4 &l = prev_lo[j], &h = prev_hi[j];
-                    bad |= std::isnan(l.x) || std::isnan(l.y) || std::isnan(l.z) || std::isnan(h.x) ||
-                           std::isnan(h.y) || std::isnan(h.z);
+                    const float4 &pl = prev_lo[j], &ph = prev_hi[j];
+                    bad |= std::isnan(pl.x) || std::isnan(pl.y) || std::isnan(pl.z) || std::isnan(ph.x) ||
+                           std::isnan(ph.y) || std::isnan(ph.z);
+                    // the reference's slab test takes min / max of the two planes per axis, so a
+                    // batch box with bboxMin > bboxMax on an axis (a caller's, or the builder's
+                    // untouched FLT_MAX / -FLT_MAX sentinels when every vertex is NaN there) is the
+                    // slab between the planes, not an empty one: the union orders the planes first
+                    const float4 l = make_float4(std::min(pl.x, ph.x), std::min(pl.y, ph.y), std::min(pl.z, ph.z), 0.0f);
+                    const float4 h = make_float4(std::max(pl.x, ph.x), std::max(pl.y, ph.y), std::max(pl.z, ph.z), 0.0f);
                     a.x = std::min(a.x, l.x); a.y = std::min(a.y, l.y); a.z = std::min(a.z, l.z);
                     z.x = std::max(z.x, h.x); z.y = std::max(z.y, h.y); z.z = std::max(z.z, h.z);
                 }
@@ -1848,6 +1854,23 @@ extern "C" int trt_diag_bvh_export(const trt_triangle* tris, uint32_t ntri, cons
     counts[1] = bvh_tris.size();
     if (nodes_out && bvh.size() <= cap_nodes) std::memcpy(nodes_out, bvh.data(), bvh.size() * sizeof(trt::BvhNode));
     if (tris_out && bvh_tris.size() <= cap_tris) std::memcpy(tris_out, bvh_tris.data(), bvh_tris.size() * sizeof(TriGeo));
+    return TRT_OK;
+}
+
+// Diagnostic (tests/test_mesh_cases.py), host only: the 4-wide nodes collapse_bvh4 makes of that
+// BVH2 (child refs index these nodes or the leaf references of trt_diag_bvh_export), copied out
+// when the capacity suffices; counts[0] = 4-wide nodes, counts[1] = their worst-case stack (the
+// upload keeps them only when it is <= kBvhStack).
+extern "C" int trt_diag_bvh4_export(const trt_triangle* tris, uint32_t ntri, const trt_model* models, uint32_t nmodel,
+                                    trt::Bvh4Node* nodes_out, uint32_t cap_nodes, uint64_t counts[2]) {
+    if (!counts || (ntri && !tris) || (nmodel && !models)) return TRT_ERR_INVALID;
+    std::vector<trt::BvhNode> bvh;
+    std::vector<TriGeo> bvh_tris;
+    if (!nmodel || !trt::build_bvh(tris, ntri, models, nmodel, bvh, bvh_tris)) return TRT_ERR_INVALID;
+    std::vector<trt::Bvh4Node> bvh4;
+    counts[1] = trt::collapse_bvh4(bvh, bvh4);
+    counts[0] = bvh4.size();
+    if (nodes_out && bvh4.size() <= cap_nodes) std::memcpy(nodes_out, bvh4.data(), bvh4.size() * sizeof(trt::Bvh4Node));
     return TRT_OK;
 }
 
