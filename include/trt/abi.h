@@ -357,6 +357,62 @@ int trt_check_rays(const trt_qray* rays, uint32_t n, uint32_t* first_bad);
 int trt_pixel_ray(const trt_params* p, const trt_view* v, const float cam[3],
                   uint32_t x, uint32_t y, trt_qray* out);
 
+/* ---- occlusion queries: any hit over caller segments, one byte each --------------------------
+ * trt_trace_rays answers "what does this ray hit first"; an occlusion query answers the other
+ * half: does ANYTHING lie between this point and that one — light visibility, ambient occlusion,
+ * line of sight, form-factor sampling.  It is the shader's any-hit walk (shadow_intersect,
+ * shader.comp:364-399) over the caller's segments, and it returns one byte per segment instead of
+ * a 32-byte hit record.
+ *
+ * What segment i is: the ray from `org` in direction d = normalize(dir), the shader's own
+ * normalize (shader.comp:593), exactly as trt_trace_rays treats a ray, cut off at distance tmax.
+ *   out[i] = TRT_OCC_OCCLUDED  iff  scene_intersect(org, d) finds something at a distance t < tmax,
+ * else TRT_OCC_VISIBLE: the strict `<` and the MIN_EPSILON lower bound (t > 1e-4) the shader uses
+ * everywhere (shader.comp:305, 349, 372, 389).  t and tmax are in world units along d: the t that
+ * trt_qhit.t reports.  So for any valid ray
+ *   occluded(ray, tmax) == (hit.t < tmax),   hit = the ray's trt_trace_rays record,
+ * and since a miss is t = 1e10, tmax = TRT_QSEG_MAX_T ("a whole ray") never reports a miss as
+ * occluded.  A tmax at or below MIN_EPSILON is valid and always visible.
+ *
+ * Read from p: flags only.  TRT_FLAG_FLOOR: the floor occludes, by scene_intersect's floor test
+ * (shader.comp:302-320).  Without TRT_FLAG_FLOOR the query is exactly the shader's
+ * shadow_intersect, which leaves the floor out: a caller reproducing the shader's shadow rays
+ * clears the flag.  SPHERES, BATCH_WALK, DEVICE_PTRS and TIMING are honoured as by trt_trace_rays.
+ * TRT_FLAG_COUNT is TRT_ERR_INVALID (any-hit counters depend on the walk order).  Every other
+ * field of p, max_depth included, and every other flag is ignored.  st may be NULL unless
+ * TRT_FLAG_TIMING is set (then st->kernel_ms is filled and the rest zeroed).
+ *
+ * A valid segment: a valid ray (above: six finite floats, direction length in range) with
+ * 0 < tmax <= TRT_QSEG_MAX_T; a NaN tmax is not valid.  The host checker and the kernel share one
+ * predicate.  A host-pointer call validates every segment before anything is launched: a bad one
+ * returns TRT_ERR_INVALID with the lowest bad index in trt_last_error and `out` untouched.  A
+ * device-pointer call cannot be checked on the host, so the kernel writes TRT_OCC_BAD_SEG for a bad
+ * record and traces nothing for it; the other segments of its wave are unaffected.
+ *
+ * Sizes, stream and buffers as trt_trace_rays: nsegs == 0 is TRT_OK and launches nothing; nsegs >
+ * TRT_QRAY_MAX_RAYS, or a NULL segs or out with nsegs > 0, is TRT_ERR_INVALID; a call before
+ * trt_upload_scene is TRT_ERR_NOSCENE.  With TRT_FLAG_DEVICE_PTRS `segs` must be 16-byte aligned
+ * (else TRT_ERR_INVALID; `out` needs no alignment), and without TIMING the call only enqueues on
+ * the context's stream (trt_set_stream applies).  Host pointers are synchronous and go through
+ * context-owned staging buffers that only grow.  Meshes are traced by the path trt_render takes
+ * for the scene.  The call changes nothing a later trt_render or trt_trace_rays depends on. */
+typedef struct trt_qseg { float org[3]; float tmax; float dir[3]; float pad; } trt_qseg; /* 32 B */
+#define TRT_OCC_VISIBLE 0u
+#define TRT_OCC_OCCLUDED 1u
+#define TRT_OCC_BAD_SEG 0xffu
+#define TRT_QSEG_MAX_T 1e10f /* the shader's initial nearest distance: "a whole ray" */
+#ifdef __cplusplus
+static_assert(sizeof(trt_qseg) == 32, "segment records are 32 B");
+#else
+_Static_assert(sizeof(trt_qseg) == 32, "segment records are 32 B");
+#endif
+
+int trt_occluded(trt_ctx* ctx, const trt_params* p, const trt_qseg* segs, uint32_t nsegs,
+                 uint8_t* out, trt_stats* st);
+/* host only, no context: TRT_OK when every segment is valid, else TRT_ERR_INVALID with the lowest
+ * bad index in *first_bad (may be NULL).  segs NULL with n > 0 is TRT_ERR_INVALID (*first_bad = 0). */
+int trt_check_segs(const trt_qseg* segs, uint32_t n, uint32_t* first_bad);
+
 /* Device time per frame (ms) of each launch timed by the last timed trt_render_frames call:
  * the launch's event span divided by the frames it traced (waits for them); n <= the number
  * of timed launches, trt_timed_launches(). */

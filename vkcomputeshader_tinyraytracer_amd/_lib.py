@@ -84,6 +84,8 @@ def lib() -> ctypes.CDLL:
         "trt_trace_rays": (c_int, [vp, ctypes.POINTER(Params), vp, c_u32, vp, vp, vp, ctypes.POINTER(Stats)]),
         "trt_check_rays": (c_int, [vp, c_u32, ctypes.POINTER(c_u32)]),
         "trt_pixel_ray": (c_int, [ctypes.POINTER(Params), vp, f3, c_u32, c_u32, vp]),
+        "trt_occluded": (c_int, [vp, ctypes.POINTER(Params), vp, c_u32, vp, ctypes.POINTER(Stats)]),
+        "trt_check_segs": (c_int, [vp, c_u32, ctypes.POINTER(c_u32)]),
         "trt_frame_times": (c_int, [vp, ctypes.POINTER(ctypes.c_float), c_u32]),
         "trt_timed_launches": (c_u32, [vp, ctypes.POINTER(c_u32), c_u32]),
         "trt_set_frame_batch": (c_int, [vp, c_u32]),
@@ -170,6 +172,8 @@ ABI_SYMBOLS = (
     "trt_trace_rays",
     "trt_check_rays",
     "trt_pixel_ray",
+    "trt_occluded",
+    "trt_check_segs",
     "trt_frame_times",
     "trt_timed_launches",
     "trt_set_frame_batch",

@@ -3288,6 +3288,65 @@ hipError_t launch_ray_query(const KArgs& A0, const float4* rays, uint32_t n, uin
 }
 #endif
 
+// Occlusion queries (abi.h trt_occluded): one lane per caller segment, 64 consecutive records per
+// one-wave workgroup (two 16-byte loads per lane, as ray_query_kernel), one byte out per lane: a
+// wave's 64 bytes are contiguous, one vector byte store per lane.  out[i] = "scene_intersect(org,
+// d) finds something nearer than tmax": the floor by scene_intersect's own arithmetic when
+// TRT_FLAG_FLOOR is set, the spheres and meshes by shadow_intersect as the frame kernels call it.
+// A lane whose record fails the shared predicate (trt_qray.h) traces nothing and stores
+// TRT_OCC_BAD_SEG.  The lanes that reach shadow_intersect are then any subset of the wave: bad
+// lanes, the ragged tail (i >= n) and floor-occluded lanes are gone.  The walks take that: every
+// wave-uniform value is read from the first ACTIVE lane (readfirstlane), ballots cover the active
+// lanes, walk_batches stages by active-lane rank, shadow_wave_q's stack writer is the first active
+// lane — the frame kernels call it from whichever lanes sit at a hit — and with one wave per
+// workgroup a lane that left holds nobody at an LDS barrier.
+template <int GEOM>
+__global__ __launch_bounds__(64, waves_per_simd<GEOM>()) void occlusion_query_kernel(
+    KArgs A, const float4* __restrict__ segs, uint32_t n, uint8_t* __restrict__ out) {
+    __shared__ float4 slab[slab_float4s<GEOM>()];
+    const uint32_t i = blockIdx.x * 64u + threadIdx.x;
+    if (i >= n) return;
+    const float4 a = segs[2 * (size_t)i], b = segs[2 * (size_t)i + 1];
+    const float tmax = a.w;
+    uint32_t r = TRT_OCC_BAD_SEG;
+    if (qseg_valid(a.x, a.y, a.z, b.x, b.y, b.z, tmax)) {
+        const f3 o = mk(a.x, a.y, a.z);
+        const f3 d = normalize3(mk(b.x, b.y, b.z)); // shader.comp:593
+        bool occ = false;
+        if (A.flags & TRT_FLAG_FLOOR) { // scene_intersect's floor test with tmax for the nearest (tmax <= 1e10)
+            if (fabsf(d.y) > TRT_EPS) {
+                const float t = div_rn(-(o.y + 4.0f), d.y);
+                if (t > TRT_EPS && t < tmax) {
+                    const f3 p = add(o, muls(d, t));
+                    occ = fabsf(p.x) < 10.0f && p.z < -5.0f && p.z > -30.0f;
+                }
+            }
+        }
+        if (!occ) {
+            Cnt cnt;
+            occ = shadow_intersect<false, GEOM>(A, o, d, tmax, cnt, slab);
+        }
+        r = occ ? TRT_OCC_OCCLUDED : TRT_OCC_VISIBLE;
+    }
+    out[i] = (uint8_t)r;
+}
+
+#ifndef TRT_KRES_ONLY
+hipError_t launch_occlusion_query(const KArgs& A0, const float4* segs, uint32_t n, uint8_t* out, hipStream_t stream) {
+    if (!n) return hipSuccess;
+    KArgs A = A0;
+    A.diag = nullptr;
+    // the geometry path exactly as launch_ray_query chooses it
+    const int geom = A.nbatch == 0 ? 0 : (A.bvh && !(A.flags & TRT_FLAG_BATCH_WALK)) ? (A.bvh_waves4 ? 3 : 2) : 1;
+    const dim3 grid((n + 63u) / 64u), block(64);
+    if (geom == 0) hipLaunchKernelGGL(occlusion_query_kernel<0>, grid, block, 0, stream, A, segs, n, out);
+    else if (geom == 1) hipLaunchKernelGGL(occlusion_query_kernel<1>, grid, block, 0, stream, A, segs, n, out);
+    else if (geom == 2) hipLaunchKernelGGL(occlusion_query_kernel<2>, grid, block, 0, stream, A, segs, n, out);
+    else hipLaunchKernelGGL(occlusion_query_kernel<3>, grid, block, 0, stream, A, segs, n, out);
+    return hipGetLastError();
+}
+#endif
+
 // Launch helper: picks the deferred-stack capacity from max_depth (children are made only
 // for depth+1 < max_depth, so at most max_depth-1 refraction children wait at once; inside a
 // split window of w depths at most w - 1 do, so split launches keep w - 1 in LDS).  With a

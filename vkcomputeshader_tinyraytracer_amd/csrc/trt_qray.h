@@ -24,4 +24,11 @@ __host__ __device__ inline bool qray_valid(float ox, float oy, float oz, float d
            qray_finite(dz) && s >= TRT_QRAY_MIN_LEN2 && s <= TRT_QRAY_MAX_LEN2;
 }
 
+// A segment of an occlusion query (abi.h trt_qseg; trt_check_segs, trt_occluded with host pointers
+// and occlusion_query_kernel): a valid ray cut off at 0 < tmax <= TRT_QSEG_MAX_T.  Both comparisons
+// are false for a NaN; a subnormal tmax is positive on both sides (denormals are kept).
+__host__ __device__ inline bool qseg_valid(float ox, float oy, float oz, float dx, float dy, float dz, float tmax) {
+    return qray_valid(ox, oy, oz, dx, dy, dz) && tmax > 0.0f && tmax <= TRT_QSEG_MAX_T;
+}
+
 } // namespace trt

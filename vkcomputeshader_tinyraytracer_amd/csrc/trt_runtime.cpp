@@ -42,6 +42,7 @@ hipError_t launch_sky(const KArgs& A, uint32_t* out, hipStream_t stream);
 hipError_t launch_shadow_batch(const KArgs& A, const float4* rays, uint32_t n, uint32_t* occ, hipStream_t stream);
 hipError_t launch_ray_query(const KArgs& A, const float4* rays, uint32_t n, uint32_t* out8, float4* out32, uint4* hits,
                             bool count, hipStream_t stream);
+hipError_t launch_occlusion_query(const KArgs& A, const float4* segs, uint32_t n, uint8_t* out, hipStream_t stream);
 uint32_t collapse_bvh4(const std::vector<BvhNode>& b2, std::vector<Bvh4Node>& b4);
 uint32_t bvh_depth(const std::vector<BvhNode>& b2);
 bool quantize_bvh4(const std::vector<Bvh4Node>& b4, std::vector<Bvh4QNode>& out);
@@ -278,6 +279,20 @@ int trt_check_rays(const trt_qray* rays, uint32_t n, uint32_t* first_bad) {
     for (uint32_t i = 0; i < n; ++i) {
         const trt_qray& r = rays[i];
         if (!trt::qray_valid(r.org[0], r.org[1], r.org[2], r.dir[0], r.dir[1], r.dir[2])) {
+            if (first_bad) *first_bad = i;
+            return TRT_ERR_INVALID;
+        }
+    }
+    return TRT_OK;
+}
+
+int trt_check_segs(const trt_qseg* segs, uint32_t n, uint32_t* first_bad) {
+    if (first_bad) *first_bad = 0;
+    if (n == 0) return TRT_OK;
+    if (!segs) return TRT_ERR_INVALID;
+    for (uint32_t i = 0; i < n; ++i) {
+        const trt_qseg& s = segs[i];
+        if (!trt::qseg_valid(s.org[0], s.org[1], s.org[2], s.dir[0], s.dir[1], s.dir[2], s.tmax)) {
             if (first_bad) *first_bad = i;
             return TRT_ERR_INVALID;
         }
@@ -1671,6 +1686,70 @@ int trt_trace_rays(trt_ctx* c, const trt_params* p, const trt_qray* rays, uint32
             HIP_TRY(c, hipEventElapsedTime(&ms, c->ev0, c->ev1));
             st->kernel_ms = ms;
         }
+    }
+    return TRT_OK;
+}
+
+// Occlusion queries (abi.h): the caller's segments through occlusion_query_kernel, one byte each.
+// Like trt_trace_rays it writes nothing of the context that a frame or a ray query depends on; host
+// arrays stage through the ray-query record buffer and the RGBA8 buffer (both only grow).
+int trt_occluded(trt_ctx* c, const trt_params* p, const trt_qseg* segs, uint32_t nsegs, uint8_t* out, trt_stats* st) {
+    if (!c) return TRT_ERR_INVALID;
+    if (!p) return fail(c, TRT_ERR_INVALID, "trt_occluded: null params");
+    if (!c->have_scene) return fail(c, TRT_ERR_NOSCENE, "trt_occluded: no scene uploaded");
+    if (p->flags & TRT_FLAG_COUNT)
+        return fail(c, TRT_ERR_INVALID, "trt_occluded: TRT_FLAG_COUNT is not offered (any-hit counters depend on the walk order)");
+    if ((p->flags & TRT_FLAG_TIMING) && !st) return fail(c, TRT_ERR_INVALID, "trt_occluded: TRT_FLAG_TIMING needs stats");
+    if (nsegs > TRT_QRAY_MAX_RAYS) return fail(c, TRT_ERR_INVALID, "trt_occluded: more than 2^28 segments");
+    if (nsegs && !segs) return fail(c, TRT_ERR_INVALID, "trt_occluded: null segs");
+    if (nsegs && !out) return fail(c, TRT_ERR_INVALID, "trt_occluded: null out");
+    const bool dev = (p->flags & TRT_FLAG_DEVICE_PTRS) != 0;
+    // the kernel reads a segment as two 16-byte vectors straight from the caller's device array
+    // and stores single bytes (host arrays are staged)
+    if (dev && (reinterpret_cast<uintptr_t>(segs) & 15u))
+        return fail(c, TRT_ERR_INVALID, "trt_occluded: device segs must be 16-byte aligned");
+    const bool timing = (p->flags & TRT_FLAG_TIMING) != 0;
+    if (st) std::memset(st, 0, sizeof(*st));
+    if (nsegs == 0) return TRT_OK;
+    if (!dev) { // a device array cannot be read here: the kernel applies the same predicate
+        uint32_t bad = 0;
+        if (trt_check_segs(segs, nsegs, &bad) != TRT_OK)
+            return fail(c, TRT_ERR_INVALID, "trt_occluded: segment " + std::to_string(bad) +
+                                                " is not valid (non-finite, direction length or tmax out of range)");
+    }
+    HIP_TRY(c, hipSetDevice(c->device));
+
+    // what the query reads of p, in a frame-shaped trt_params for fill_args (as trt_trace_rays)
+    trt_params q;
+    trt_params_default(&q);
+    q.width = 64;
+    q.height = 1;
+    q.max_depth = 1;
+    q.flags = p->flags & (TRT_FLAG_SPHERES | TRT_FLAG_FLOOR | TRT_FLAG_BATCH_WALK | TRT_FLAG_DEVICE_PTRS | TRT_FLAG_TIMING);
+    int rc;
+    KArgs A;
+    fill_args(c, &q, A);
+    A.view_on = 0;
+
+    const float4* d_segs = reinterpret_cast<const float4*>(segs);
+    uint8_t* d_out = out;
+    const size_t n = nsegs;
+    if (!dev) {
+        if ((rc = ensure(c, &c->d_qrays, &c->capqrays, n * sizeof(trt_qseg), "alloc query segments")) != TRT_OK) return rc;
+        if ((rc = ensure(c, &c->d_out8, &c->cap8, n, "alloc occlusion bytes")) != TRT_OK) return rc;
+        HIP_TRY(c, hipMemcpyAsync(c->d_qrays, segs, n * sizeof(trt_qseg), hipMemcpyHostToDevice, c->stream));
+        d_segs = static_cast<const float4*>(c->d_qrays);
+        d_out = reinterpret_cast<uint8_t*>(c->d_out8);
+    }
+    if (timing) HIP_TRY(c, hipEventRecord(c->ev0, c->stream));
+    HIP_TRY(c, trt::launch_occlusion_query(A, d_segs, nsegs, d_out, c->stream));
+    if (timing) HIP_TRY(c, hipEventRecord(c->ev1, c->stream));
+    if (!dev) HIP_TRY(c, hipMemcpyAsync(out, c->d_out8, n, hipMemcpyDeviceToHost, c->stream));
+    if (!dev || timing) HIP_TRY(c, hipStreamSynchronize(c->stream));
+    if (timing) {
+        float ms = 0.0f;
+        HIP_TRY(c, hipEventElapsedTime(&ms, c->ev0, c->ev1));
+        st->kernel_ms = ms;
     }
     return TRT_OK;
 }

@@ -252,6 +252,56 @@ class Renderer:
                                            ctypes.byref(st)))
         return out8, out32, hits, st.as_dict()
 
+    # -- occlusion queries -------------------------------------------------------------------
+    def occluded(self, segs, params: T.Params, *, out=None, timing: bool = False, nsegs: int | None = None):
+        """Any-hit over the caller's segments (trt_occluded): is anything nearer than `tmax` along
+        normalize(dir) from `org`?  `segs` is a numpy array of T.QSEG (host, synchronous, every
+        segment validated first: a bad one raises TrtError and leaves `out` untouched) or a
+        contiguous torch CUDA tensor holding such records (device pointers, 16-byte aligned, only
+        enqueued on the context's stream unless timing; a segment that is not valid reads
+        T.OCC_BAD_SEG).  Of `params` only the flags are read: FLOOR (the floor occludes; clear it
+        for the shader's own shadow rays), SPHERES, BATCH_WALK; FLAG_COUNT is refused
+        (T.TRT_ERR_INVALID).  `out` is made on the side of the segments unless given (it may be
+        longer than the query; bytes past it are untouched); `nsegs` limits the query to the first
+        segments.
+        Returns the (n,) uint8 array or tensor of T.OCC_VISIBLE / T.OCC_OCCLUDED, or with `timing`
+        the pair (bytes, stats_dict)."""
+        p = T.Params.from_buffer_copy(params)
+        p.rays_in = None
+        if _is_torch_cuda(segs):
+            import torch
+
+            if not segs.is_contiguous():
+                raise ValueError("segs must be a contiguous device tensor of T.QSEG records")
+            have = segs.numel() * segs.element_size() // T.QSEG.itemsize
+            n = have if nsegs is None else int(nsegs)
+            if n > have:
+                raise ValueError(f"{n} segments asked of a tensor that holds {have}")
+            p.flags |= T.FLAG_DEVICE_PTRS
+            if out is None:
+                out = torch.empty((n,), dtype=torch.uint8, device=segs.device)
+            if not (_is_torch_cuda(out) and out.is_contiguous() and out.numel() * out.element_size() >= n):
+                raise ValueError("the output of a device query is a contiguous device tensor that holds every segment")
+            ptrs = (segs.data_ptr(), out.data_ptr())
+        else:
+            p.flags &= ~T.FLAG_DEVICE_PTRS
+            s = None if segs is None else np.ascontiguousarray(segs, T.QSEG).reshape(-1)
+            n = (0 if s is None else s.shape[0]) if nsegs is None else int(nsegs)
+            if s is not None and n > s.shape[0]:
+                raise ValueError(f"{n} segments asked of an array that holds {s.shape[0]}")
+            if out is None:
+                out = np.empty((n,), np.uint8)
+            if not (isinstance(out, np.ndarray) and out.flags["C_CONTIGUOUS"] and out.dtype == np.uint8 and out.size >= n):
+                raise ValueError("the output of a host query is a C-contiguous uint8 numpy array that holds every segment")
+            ptrs = (None if s is None or not len(s) else s.ctypes.data, out.ctypes.data)
+        if timing:
+            p.flags |= T.FLAG_TIMING
+        else:
+            p.flags &= ~T.FLAG_TIMING
+        st = T.Stats()
+        self._check(self._L.trt_occluded(self._h, ctypes.byref(p), ptrs[0], n, ptrs[1], ctypes.byref(st)))
+        return (out, st.as_dict()) if timing else out
+
     def pixel_ray(self, params: T.Params, x: int, y: int) -> np.ndarray:
         """The T.QRAY of pixel (x, y)'s primary ray at spp 1 under the context's current UBO
         (camPos) and view (trt_pixel_ray)."""

@@ -186,6 +186,37 @@ def equirect_qrays(width: int, height: int, cam=(0.0, 0.0, 0.0)) -> np.ndarray:
     return q
 
 
+def segments_between(a, b) -> np.ndarray:
+    """"Can a see b": the T.QSEG records of Renderer.occluded for the segments from points `a` to
+    points `b` ((..., 3) each, broadcast against each other): org = a, dir = b - a and tmax =
+    |b - a|, all in float32 — the length as sqrt((x * x + y * y) + z * z) in the project's dot
+    order, the sum the kernel normalizes the direction by.  A surface at b itself does not occlude
+    (the test is t < tmax); start a little off a surface at a, as the shader's shadow rays do."""
+    a = np.asarray(a, np.float32)
+    b = np.asarray(b, np.float32)
+    a, b = np.broadcast_arrays(a, b)
+    if a.shape[-1] != 3:
+        raise ValueError("points are (..., 3) arrays")
+    d = (b - a).astype(np.float32)
+    x, y, z = d[..., 0], d[..., 1], d[..., 2]
+    s = np.zeros(a.shape[:-1], T.QSEG)
+    s["org"] = a
+    s["dir"] = d
+    s["tmax"] = np.sqrt((x * x + y * y) + z * z, dtype=np.float32)
+    return s
+
+
+def segments_from_rays(qrays, tmax=T.QSEG_MAX_T) -> np.ndarray:
+    """T.QRAY records as T.QSEG records of the same shape: origin and direction copied, cut off at
+    `tmax` (a scalar or one per ray; the default is a whole ray: occluded = the ray hits anything)."""
+    r = np.asarray(qrays, T.QRAY)
+    s = np.zeros(r.shape, T.QSEG)
+    s["org"] = r["org"]
+    s["dir"] = r["dir"]
+    s["tmax"] = np.asarray(tmax, np.float32)
+    return s
+
+
 def camera_orbit(ubo: np.ndarray, n: int, speed: float = 0.02, yaw_step: float = 1.0, pitch_step: float = -0.25,
                  yaw0: float = 0.0, pitch0: float = 0.0) -> tuple[np.ndarray, np.ndarray]:
     """camera_path with a camera that turns while it walks (mouse look held with W and D): n

@@ -58,6 +58,13 @@ HIT_BAD_RAY = 0xFFFFFFFF  # a device-pointer query's record of a ray that is not
 QRAY_MIN_LEN2 = np.float32(1e-30)  # TRT_QRAY_MIN_LEN2 / MAX_LEN2: bounds of the direction's squared length
 QRAY_MAX_LEN2 = np.float32(1e30)
 QRAY_MAX_RAYS = 1 << 28
+# abi.h trt_qseg: a segment of an occlusion query (Renderer.occluded), a ray cut off at tmax
+QSEG = np.dtype([("org", "<f4", (3,)), ("tmax", "<f4"), ("dir", "<f4", (3,)), ("pad", "<f4")])
+OCC_VISIBLE = 0
+OCC_OCCLUDED = 1
+OCC_BAD_SEG = 0xFF  # a device-pointer query's byte for a segment that is not valid
+QSEG_MAX_T = np.float32(1e10)  # TRT_QSEG_MAX_T: the shader's initial nearest distance, "a whole ray"
+assert QSEG.itemsize == 32
 
 assert VIEW.itemsize == 36 and QRAY.itemsize == 32 and QHIT.itemsize == 32
 assert MATERIAL.itemsize == 48 and SPHERE.itemsize == 64
