@@ -5,31 +5,18 @@ the C2 kernel has no scratch at all, the C4 kernel stays near its measured spill
 from __future__ import annotations
 
 import re
-import subprocess
-import sys
-from pathlib import Path
 
 import pytest
 
-REPO = Path(__file__).resolve().parents[1]
-OBJ = REPO / "build" / "csrc" / "trt_kernel.o"
+from tests.kres_common import OBJ, kres
 
 
 @pytest.fixture(scope="module")
 def resources():
     if not OBJ.exists():
         pytest.skip("build/csrc/trt_kernel.o not built")
-    out = subprocess.run([sys.executable, str(REPO / "tools" / "kres.py"), "trace_kernel"], check=True,
-                         capture_output=True, text=True).stdout
-    res = {}
-    for line in out.splitlines():
-        m = re.match(r"void trt::trace_kernel<([^>]*)>\(trt::KArgs\)\s+vgpr\s+(\d+)\s+sgpr\s+(\d+)\s+scratch\s+(\d+)\s+lds\s+(\d+)",
-                     line)
-        if m:
-            res[m.group(1)] = dict(vgpr=int(m.group(2)), sgpr=int(m.group(3)), scratch=int(m.group(4)),
-                                   lds=int(m.group(5)))
-    assert res, out[:500]
-    return res
+    return {m.group(1): r for name, r in kres("trace_kernel").items()
+            if (m := re.fullmatch(r"void trt::trace_kernel<([^>]*)>\(trt::KArgs\)", name))}
 
 
 def test_c2_kernel_has_no_scratch(resources):

@@ -9,27 +9,18 @@ __launch_bounds__ ask for (the same waves_per_simd<GEOM>() as the yardstick)."""
 from __future__ import annotations
 
 import re
-import subprocess
-import sys
-from pathlib import Path
 
 import pytest
 
-REPO = Path(__file__).resolve().parents[1]
-OBJ = REPO / "build" / "csrc" / "trt_kernel.o"
+from tests.kres_common import OBJ, REPO, kres
+
 KERNEL_SRC = REPO / "vkcomputeshader_tinyraytracer_amd" / "csrc" / "trt_kernel.hip"
 
 
 def _kres(kernel: str) -> dict:
-    out = subprocess.run([sys.executable, str(REPO / "tools" / "kres.py"), kernel], check=True, capture_output=True,
-                         text=True).stdout
-    res = {}
-    for line in out.splitlines():
-        m = re.match(rf"void trt::{kernel}<(\d)>\(trt::KArgs.*\)\s+vgpr\s+(\d+)\s+sgpr\s+(\d+)\s+scratch\s+(\d+)\s+lds\s+(\d+)", line)
-        if m:
-            res[int(m.group(1))] = dict(vgpr=int(m.group(2)), sgpr=int(m.group(3)), scratch=int(m.group(4)),
-                                        lds=int(m.group(5)))
-    assert sorted(res) == [0, 1, 2, 3], out[:500]
+    res = {int(m.group(1)): r for name, r in kres(kernel).items()
+           if (m := re.fullmatch(rf"void trt::{kernel}<(\d)>\(trt::KArgs.*\)", name))}
+    assert sorted(res) == [0, 1, 2, 3], res
     return res
 
 

@@ -8,14 +8,10 @@ whole struct lives in scratch and a frame is ~20x slower."""
 from __future__ import annotations
 
 import re
-import subprocess
-import sys
-from pathlib import Path
 
 import pytest
 
-REPO = Path(__file__).resolve().parents[1]
-OBJ = REPO / "build" / "csrc" / "trt_kernel.o"
+from tests.kres_common import OBJ, kres
 
 # trace_kernel<CAP, COUNT, GEOM, SPLIT, DEFER, HYB>: the plain GEOM 0 launches (trt_kernel.hip
 # launch_trace) by their deferred-stack capacity; CAP <= 4 keeps the stack in LDS.
@@ -26,15 +22,8 @@ PLAIN_G0 = (0, 1, 2, 3, 4, 7, 19)
 def resources():
     # a missing object is a failed or skipped kernel build, not a missing GPU: fail, do not skip
     assert OBJ.exists(), "build/csrc/trt_kernel.o is missing: run __graft_entry__.build() first"
-    out = subprocess.run([sys.executable, str(REPO / "tools" / "kres.py"), "trace_kernel|sky_kernel"], check=True,
-                         capture_output=True, text=True).stdout
-    res = {}
-    for line in out.splitlines():
-        m = re.match(r"(?:void )?trt::(\w+)(?:<([^>]*)>)?\(.*?\)\s+vgpr\s+(\d+)\s+sgpr\s+(\d+)\s+scratch\s+(\d+)", line)
-        if m:
-            res[(m.group(1), m.group(2))] = dict(vgpr=int(m.group(3)), sgpr=int(m.group(4)), scratch=int(m.group(5)))
-    assert res, out[:500]
-    return res
+    return {(m.group(1), m.group(2)): r for name, r in kres("trace_kernel|sky_kernel").items()
+            if (m := re.fullmatch(r"(?:void )?trt::(\w+)(?:<([^>]*)>)?\(.*\)", name))}
 
 
 @pytest.mark.parametrize("cap", PLAIN_G0)

@@ -6,14 +6,11 @@ no more LDS than sky_trace_kernel of the same CAP, the kernel a launch without m
 from __future__ import annotations
 
 import re
-import subprocess
-import sys
-from pathlib import Path
 
 import pytest
 
-REPO = Path(__file__).resolve().parents[1]
-OBJ = REPO / "build" / "csrc" / "trt_kernel.o"
+from tests.kres_common import OBJ, kres
+
 PLAIN_G0 = (0, 1, 2, 3, 4, 7, 19)
 
 
@@ -21,16 +18,8 @@ PLAIN_G0 = (0, 1, 2, 3, 4, 7, 19)
 def resources():
     # a missing object is a failed or skipped kernel build, not a missing GPU: fail, do not skip
     assert OBJ.exists(), "build/csrc/trt_kernel.o is missing: run __graft_entry__.build() first"
-    out = subprocess.run([sys.executable, str(REPO / "tools" / "kres.py"), "sky_trace_kernel"], check=True,
-                         capture_output=True, text=True).stdout
-    res = {}
-    for line in out.splitlines():
-        m = re.match(r"(?:void )?trt::(\w+)<(\d+)>\(.*?\)\s+vgpr\s+(\d+)\s+sgpr\s+(\d+)\s+scratch\s+(\d+)\s+lds\s+(\d+)", line)
-        if m:
-            res[(m.group(1), int(m.group(2)))] = dict(vgpr=int(m.group(3)), sgpr=int(m.group(4)),
-                                                      scratch=int(m.group(5)), lds=int(m.group(6)))
-    assert res, out[:500]
-    return res
+    return {(m.group(1), int(m.group(2))): r for name, r in kres("sky_trace_kernel").items()
+            if (m := re.fullmatch(r"(?:void )?trt::(\w+)<(\d+)>\(.*\)", name))}
 
 
 @pytest.mark.parametrize("cap", PLAIN_G0)

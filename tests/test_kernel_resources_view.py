@@ -11,31 +11,18 @@ pinned by tests/test_kernel_resources_sky.py, _spans, _smask and _floor, unchang
 from __future__ import annotations
 
 import re
-import subprocess
-import sys
-from pathlib import Path
 
 import pytest
 
-REPO = Path(__file__).resolve().parents[1]
-OBJ = REPO / "build" / "csrc" / "trt_kernel.o"
+from tests.kres_common import OBJ, REPO, kres
 
 
 @pytest.fixture(scope="module")
 def resources():
     if not OBJ.exists():
         pytest.skip("build/csrc/trt_kernel.o not built")
-    out = subprocess.run([sys.executable, str(REPO / "tools" / "kres.py"), "trace_kernel"], check=True,
-                         capture_output=True, text=True).stdout
-    res = {}
-    for line in out.splitlines():
-        m = re.match(r"void trt::trace_kernel<([^>]*)>\(trt::KArgs\)\s+vgpr\s+(\d+)\s+sgpr\s+(\d+)\s+scratch\s+(\d+)\s+lds\s+(\d+)",
-                     line)
-        if m:
-            res[m.group(1)] = dict(vgpr=int(m.group(2)), sgpr=int(m.group(3)), scratch=int(m.group(4)),
-                                   lds=int(m.group(5)))
-    assert res, out[:500]
-    return res
+    return {m.group(1): r for name, r in kres("trace_kernel").items()
+            if (m := re.fullmatch(r"void trt::trace_kernel<([^>]*)>\(trt::KArgs\)", name))}
 
 
 @pytest.mark.parametrize("cap", [0, 1, 2, 3, 4])

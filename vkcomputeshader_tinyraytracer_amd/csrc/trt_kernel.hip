@@ -28,7 +28,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-
+#include <type_traits>
 
 #include "../../include/trt/abi.h"
 #include "trt_bands.h"
@@ -272,6 +272,11 @@ __device__ __forceinline__ void walk_batches(const KArgs& A, f3 o, f3 d, f3 inv,
                         const float4 ga = slab[k * 3 + 0], gb = slab[k * 3 + 1], gc = slab[k * 3 + 2];
                         if (COUNT) ++c.tt;
                         const f3 v0 = mk(ga.x, ga.y, ga.z), e1 = mk(ga.w, gb.x, gb.y), e2 = mk(gb.z, gb.w, gc.x);
+                        // Moller-Trumbore up to t > MIN_EPSILON: once more in trace_bvh, bvh_leaf and
+                        // shadow_tri_s.  One mt_test() returning {ok, u, v, t} by value kept every kernel's
+                        // resources but changed the 66 GEOM 2 / 3 kernels (tools/kres.py --diff class (b)), and
+                        // their frames did not stay within the parent's own spread, so the
+                        // copies stay; with float& out-parameters the C4 kernel spilled 32 more VGPRs
                         f3 hv = cross3(d, e2);
                         float a = dot3(e1, hv);
                         if (a > -TRT_EPS && a < TRT_EPS) continue;
@@ -395,6 +400,9 @@ constexpr int slab_words() { return bvh_lds_entries<GEOM>() * 64; }
 // flat_load that goes through the vector-memory pipe (TA/TD) even for LDS entries.
 typedef __attribute__((address_space(3))) uint32_t lds_u32;
 typedef __attribute__((address_space(3))) float lds_f32;
+// Constant address space: wave-uniform reads of the launch's read-only records (scalar loads).
+typedef __attribute__((address_space(4))) const float cfloat;
+typedef __attribute__((address_space(4))) const uint32_t cuint;
 template <int N, bool PUSH3 = false>
 struct BvhStack {
     struct Mem {
@@ -436,6 +444,12 @@ struct BvhStack {
     }
 };
 
+// A leaf reference's triangles: [first, first + n) of the BVH-ordered array, n in 1..16.
+__device__ __forceinline__ void leaf_range(uint32_t node, uint32_t& first, uint32_t& n) {
+    first = node & kBvhFirstMask;
+    n = ((node >> kBvhCountShift) & 15u) + 1u;
+}
+
 template <bool COUNT, bool SHADOW, int GEOM>
 __device__ __forceinline__ void trace_bvh(const KArgs& A, f3 o, f3 d, f3 inv, Hit& h, bool& occluded,
                                           float max_dist, Cnt& c, float4* slab) {
@@ -470,8 +484,10 @@ __device__ __forceinline__ void trace_bvh(const KArgs& A, f3 o, f3 d, f3 inv, Hi
                 continue;
             }
         } else {
-            const uint32_t first = node & kBvhFirstMask;
-            const uint32_t n = ((node >> kBvhCountShift) & 15u) + 1u;
+            // bvh_leaf without its prefetch: calling bvh_leaf here kept every resource but cost the
+            // GEOM 2 frames 0.5 % (profiles/walk_blocks_bisect.jsonl), so this copy stays
+            uint32_t first, n;
+            leaf_range(node, first, n);
             for (uint32_t k = first; k < first + n; ++k) {
                 const TriGeo g = A.bvh_tris[k];
                 if (COUNT) ++c.tt;
@@ -534,8 +550,8 @@ __device__ __forceinline__ void trace_bvh(const KArgs& A, f3 o, f3 d, f3 inv, Hi
 template <bool COUNT, bool SHADOW>
 __device__ __forceinline__ bool bvh_leaf(const KArgs& A, uint32_t node, f3 o, f3 d, f3 inv, Hit& h,
                                          float max_dist, float& best, Cnt& c) {
-    const uint32_t first = node & kBvhFirstMask;
-    const uint32_t n = ((node >> kBvhCountShift) & 15u) + 1u;
+    uint32_t first, n;
+    leaf_range(node, first, n);
 #ifndef TRT_LEAF_PREFETCH
 #define TRT_LEAF_PREFETCH 1
 #endif
@@ -598,7 +614,6 @@ __device__ __forceinline__ bool bvh_leaf(const KArgs& A, uint32_t node, f3 o, f3
 // bvh_leaf's test term for term (Moller-Trumbore, t in (MIN_EPSILON, max_dist), the reference's
 // batch gate), so a hit is a genuine occluder of this lane's query.
 __device__ __forceinline__ bool shadow_tri_s(const KArgs& A, uint32_t k, f3 o, f3 d, float max_dist) {
-    typedef __attribute__((address_space(4))) const float cfloat;
     const cfloat* T = (const cfloat*)(A.bvh_tris + k);
     const f3 v0 = mk(T[0], T[1], T[2]), e1 = mk(T[3], T[4], T[5]), e2 = mk(T[6], T[7], T[8]);
     f3 hv = cross3(d, e2);
@@ -618,6 +633,51 @@ __device__ __forceinline__ bool shadow_tri_s(const KArgs& A, uint32_t k, f3 o, f
     const cfloat* B = (const cfloat*)(A.batches + batch);
     const float bmin[3] = {B[0], B[1], B[2]}, bmax[3] = {B[3], B[4], B[5]};
     return aabb_hit(o, gate_inv(d), bmin, bmax);
+}
+
+// Five-comparator sorting network on (key, ref): ascending key, so misses (key = inf) end last.
+__device__ __forceinline__ void sort4(float (&t)[4], uint32_t (&r)[4]) {
+    auto cswap = [&](int a, int b) {
+        const bool sw = t[b] < t[a];
+        const float ta = t[a], tb = t[b];
+        const uint32_t ra = r[a], rb = r[b];
+        t[a] = sw ? tb : ta;
+        t[b] = sw ? ta : tb;
+        r[a] = sw ? rb : ra;
+        r[b] = sw ? ra : rb;
+    };
+    cswap(0, 1);
+    cswap(2, 3);
+    cswap(0, 2);
+    cswap(1, 3);
+    cswap(1, 2);
+}
+
+// A node record read through the constant address space: for a wave-uniform `n` (the root, a
+// node every lane is at, the wave-coherent shadow walk) the compiler may, and does, use scalar
+// loads, which the scalar cache serves; the BVH is read-only for the whole launch.  The
+// per-lane vector loads of a divergent node stay with their walks.
+// the quantized record (Bvh4QNode, 64 B): origin and step exponents, low / high bytes, children
+__device__ __forceinline__ void load_qnode_s(const KArgs& A, uint32_t n, float4& pe, uint4& qa, uint4& qb, uint4& ch) {
+    const cfloat* R = (const cfloat*)(A.bvh4q + n);
+    const cuint* RC = (const cuint*)(A.bvh4q + n);
+    pe = make_float4(R[0], R[1], R[2], R[3]);
+    qa = make_uint4(RC[4], RC[5], RC[6], RC[7]);
+    qb = make_uint4(RC[8], RC[9], RC[10], RC[11]);
+    ch = make_uint4(RC[12], RC[13], RC[14], RC[15]);
+}
+// the float record (Bvh4Node, 112 B): six planes of four children, children
+__device__ __forceinline__ void load_node_s(const KArgs& A, uint32_t n, float4& lx, float4& ly, float4& lz, float4& hx,
+                                            float4& hy, float4& hz, uint4& ch) {
+    const cfloat* R = (const cfloat*)(A.bvh4 + n);
+    const cuint* RC = (const cuint*)(A.bvh4 + n);
+    lx = make_float4(R[0], R[1], R[2], R[3]);
+    ly = make_float4(R[4], R[5], R[6], R[7]);
+    lz = make_float4(R[8], R[9], R[10], R[11]);
+    hx = make_float4(R[12], R[13], R[14], R[15]);
+    hy = make_float4(R[16], R[17], R[18], R[19]);
+    hz = make_float4(R[20], R[21], R[22], R[23]);
+    ch = make_uint4(RC[24], RC[25], RC[26], RC[27]);
 }
 
 #ifndef TRT_BVH_WIDTH
@@ -652,23 +712,7 @@ __device__ __forceinline__ bool visit4(f3 o, f3 inv, float best, const float4& l
     }
     if (COUNT) c.nt += (ch.x != kBvh4None) + (ch.y != kBvh4None) + (ch.z != kBvh4None) + (ch.w != kBvh4None);
     if (nh == 0) return false;
-    // sorting network on (t, ref): ascending t, misses (t = inf) last
-#define TRT_CSWAP(a, b)                                   \
-    do {                                                  \
-        const bool sw = t[b] < t[a];                      \
-        const float ta = t[a], tb = t[b];                 \
-        const uint32_t ra = r[a], rb = r[b];              \
-        t[a] = sw ? tb : ta;                              \
-        t[b] = sw ? ta : tb;                              \
-        r[a] = sw ? rb : ra;                              \
-        r[b] = sw ? ra : rb;                              \
-    } while (0)
-    TRT_CSWAP(0, 1);
-    TRT_CSWAP(2, 3);
-    TRT_CSWAP(0, 2);
-    TRT_CSWAP(1, 3);
-    TRT_CSWAP(1, 2);
-#undef TRT_CSWAP
+    sort4(t, r);
     stack.push_sorted(r, nh);
     node = r[0];
     return true;
@@ -700,7 +744,6 @@ __device__ __forceinline__ float quant_origin_term(float a) { return __builtin_f
 // patterns of non-negative floats order like their values, NaN and inf above every bound) and
 // |inv| <= 1e20 per lane, |p_node - o| * |inv| < 3e17 * 1e20.
 __device__ __forceinline__ bool quant_terms_finite(const KArgs& A, float fx, float fy, float fz, f3 inv) {
-    typedef __attribute__((address_space(4))) const uint32_t cuint;
     const cuint* R = (const cuint*)(A.bvh4q);
     constexpr uint32_t kAbs = 0x7fffffffu, k1e17 = 0x5bb1a2bcu; // 1e17f
     const uint32_t ex = R[3];
@@ -718,6 +761,9 @@ __device__ __forceinline__ bool visit4q(f3 o, f3 inv, float best, const float4& 
     const float sy = __uint_as_float(((ex >> 8) & 0xffu) << 23);
     const float sz = __uint_as_float(((ex >> 16) & 0xffu) << 23);
     // quant_origin_term: an origin term that overflowed must not put the axis' far plane at -inf
+    // (this plane arithmetic stands once more in shadow_wave_q, unguarded: as quant_planes<GUARD> /
+    // quant_child helpers it kept every kernel's resources, but the hits-only GEOM 3 query it
+    // changed ran 2 % slower than the parent's, profiles/walk_blocks_step6_query_ab.txt, so the copies stay)
     const float ax = quant_origin_term((pe.x - o.x) * inv.x), bx = sx * inv.x;
     const float ay = quant_origin_term((pe.y - o.y) * inv.y), by = sy * inv.y;
     const float az = quant_origin_term((pe.z - o.z) * inv.z), bz = sz * inv.z;
@@ -745,22 +791,7 @@ __device__ __forceinline__ bool visit4q(f3 o, f3 inv, float best, const float4& 
     }
     if (COUNT) c.nt += (ch.x != kBvh4None) + (ch.y != kBvh4None) + (ch.z != kBvh4None) + (ch.w != kBvh4None);
     if (nh == 0) return false;
-#define TRT_CSWAP(a, b)                                   \
-    do {                                                  \
-        const bool sw = t[b] < t[a];                      \
-        const float ta = t[a], tb = t[b];                 \
-        const uint32_t ra = r[a], rb = r[b];              \
-        t[a] = sw ? tb : ta;                              \
-        t[b] = sw ? ta : tb;                              \
-        r[a] = sw ? rb : ra;                              \
-        r[b] = sw ? ra : rb;                              \
-    } while (0)
-    TRT_CSWAP(0, 1);
-    TRT_CSWAP(2, 3);
-    TRT_CSWAP(0, 2);
-    TRT_CSWAP(1, 3);
-    TRT_CSWAP(1, 2);
-#undef TRT_CSWAP
+    sort4(t, r);
     stack.push_sorted(r, nh);
     node = r[0];
     return true;
@@ -800,14 +831,9 @@ __device__ __forceinline__ void trace_bvh4(const KArgs& A, f3 o, f3 d, f3 inv, H
     // (profiles/r02_ab_quant.log), so the quantized nodes serve the 4-wave build only
     if (GEOM == 3 && (g3_quant_only<GEOM>() || A.bvh4q)) {
         {
-            typedef __attribute__((address_space(4))) const float cfloat;
-            typedef __attribute__((address_space(4))) const uint32_t cuint;
-            const cfloat* R = (const cfloat*)(A.bvh4q);
-            const cuint* RC = (const cuint*)(A.bvh4q);
-            const float4 pe = make_float4(R[0], R[1], R[2], R[3]);
-            const uint4 qa = make_uint4(RC[4], RC[5], RC[6], RC[7]);
-            const uint4 qb = make_uint4(RC[8], RC[9], RC[10], RC[11]);
-            const uint4 ch = make_uint4(RC[12], RC[13], RC[14], RC[15]);
+            float4 pe;
+            uint4 qa, qb, ch;
+            load_qnode_s(A, 0u, pe, qa, qb, ch);
 #ifdef TRT_DIAG_PIXEL_WORK
             ++c.wn;
 #endif
@@ -818,17 +844,7 @@ __device__ __forceinline__ void trace_bvh4(const KArgs& A, f3 o, f3 d, f3 inv, H
             // every lane at an internal node visits the same node (coherent rays, top levels):
             // one scalar fetch for the wave instead of 4 per-lane dwordx4 loads through TA/TD
             const uint32_t n0 = __builtin_amdgcn_readfirstlane(nd);
-            if (__ballot(nd != n0) == 0ull) {
-                typedef __attribute__((address_space(4))) const float cfloat;
-                typedef __attribute__((address_space(4))) const uint32_t cuint;
-                const cfloat* R = (const cfloat*)(A.bvh4q + n0);
-                const cuint* RC = (const cuint*)(A.bvh4q + n0);
-                pe = make_float4(R[0], R[1], R[2], R[3]);
-                qa = make_uint4(RC[4], RC[5], RC[6], RC[7]);
-                qb = make_uint4(RC[8], RC[9], RC[10], RC[11]);
-                ch = make_uint4(RC[12], RC[13], RC[14], RC[15]);
-                return;
-            }
+            if (__ballot(nd != n0) == 0ull) return load_qnode_s(A, n0, pe, qa, qb, ch);
 #endif
             const float4* p = reinterpret_cast<const float4*>(A.bvh4q + nd);
             pe = p[0];
@@ -857,22 +873,12 @@ __device__ __forceinline__ void trace_bvh4(const KArgs& A, f3 o, f3 d, f3 inv, H
     if constexpr (g3_quant_only<GEOM>()) return;
 #if TRT_ROOT_SCALAR
     {
-        // constant address space: the compiler may (and, the address being uniform, does) use
-        // scalar loads; the BVH is read-only for the whole launch
-        typedef __attribute__((address_space(4))) const float cfloat;
-        typedef __attribute__((address_space(4))) const uint32_t cuint;
-        const cfloat* R = (const cfloat*)(A.bvh4);
-        const cuint* RC = (const cuint*)(A.bvh4);
 #ifdef TRT_DIAG_PIXEL_WORK
         ++c.wn;
 #endif
-        const float4 lx = make_float4(R[0], R[1], R[2], R[3]);
-        const float4 ly = make_float4(R[4], R[5], R[6], R[7]);
-        const float4 lz = make_float4(R[8], R[9], R[10], R[11]);
-        const float4 hx = make_float4(R[12], R[13], R[14], R[15]);
-        const float4 hy = make_float4(R[16], R[17], R[18], R[19]);
-        const float4 hz = make_float4(R[20], R[21], R[22], R[23]);
-        const uint4 ch = make_uint4(RC[24], RC[25], RC[26], RC[27]);
+        float4 lx, ly, lz, hx, hy, hz;
+        uint4 ch;
+        load_node_s(A, 0u, lx, ly, lz, hx, hy, hz, ch);
         if (!visit4<COUNT>(o, inv, best, lx, ly, lz, hx, hy, hz, ch, stack, node, c)) return;
     }
 #endif
@@ -883,17 +889,7 @@ __device__ __forceinline__ void trace_bvh4(const KArgs& A, f3 o, f3 d, f3 inv, H
 #if TRT_UNIFORM_NODE
             const uint32_t n0 = __builtin_amdgcn_readfirstlane(node);
             if (__ballot(node != n0) == 0ull) { // one scalar fetch for the wave (see visit4q's loop)
-                typedef __attribute__((address_space(4))) const float cfloat;
-                typedef __attribute__((address_space(4))) const uint32_t cuint;
-                const cfloat* R = (const cfloat*)(A.bvh4 + n0);
-                const cuint* RC = (const cuint*)(A.bvh4 + n0);
-                lx = make_float4(R[0], R[1], R[2], R[3]);
-                ly = make_float4(R[4], R[5], R[6], R[7]);
-                lz = make_float4(R[8], R[9], R[10], R[11]);
-                hx = make_float4(R[12], R[13], R[14], R[15]);
-                hy = make_float4(R[16], R[17], R[18], R[19]);
-                hz = make_float4(R[20], R[21], R[22], R[23]);
-                ch = make_uint4(RC[24], RC[25], RC[26], RC[27]);
+                load_node_s(A, n0, lx, ly, lz, hx, hy, hz, ch);
             } else
 #endif
             {
@@ -950,27 +946,25 @@ __device__ __forceinline__ bool ray_misses_all_batches(f3 o, f3 d) {
 #endif
 constexpr int kShadowWaveStack = 128; // >= kBvhStack
 __device__ __forceinline__ bool shadow_wave_q(const KArgs& A, f3 o, f3 d, f3 inv, float max_dist, float4* slab) {
-    typedef __attribute__((address_space(4))) const float cfloat;
-    typedef __attribute__((address_space(4))) const uint32_t cuint;
     lds_u32* ws = (lds_u32*)reinterpret_cast<uint32_t*>(slab);
     uint32_t sp = 0u, node = 0u;
     for (;;) {
         if (!(node & kBvhLeafBit)) {
-            const cfloat* R = (const cfloat*)(A.bvh4q + node);
-            const cuint* RC = (const cuint*)(A.bvh4q + node);
-            const uint32_t ex = RC[3];
+            float4 pe;
+            uint4 qa, qb, ch;
+            load_qnode_s(A, node, pe, qa, qb, ch);
+            const uint32_t ex = __float_as_uint(pe.w);
             const float sx = __uint_as_float((ex & 0xffu) << 23);
             const float sy = __uint_as_float(((ex >> 8) & 0xffu) << 23);
             const float sz = __uint_as_float(((ex >> 16) & 0xffu) << 23);
-            const float ax = (R[0] - o.x) * inv.x, bx = sx * inv.x;
-            const float ay = (R[1] - o.y) * inv.y, by = sy * inv.y;
-            const float az = (R[2] - o.z) * inv.z, bz = sz * inv.z;
-            const uint32_t qlx = RC[4], qly = RC[5], qlz = RC[6], qhx = RC[7], qhy = RC[8], qhz = RC[9];
-            const uint32_t nx = inv.x >= 0.0f ? qlx : qhx, fx = inv.x >= 0.0f ? qhx : qlx;
-            const uint32_t ny = inv.y >= 0.0f ? qly : qhy, fy = inv.y >= 0.0f ? qhy : qly;
-            const uint32_t nz = inv.z >= 0.0f ? qlz : qhz, fz = inv.z >= 0.0f ? qhz : qlz;
+            const float ax = (pe.x - o.x) * inv.x, bx = sx * inv.x;
+            const float ay = (pe.y - o.y) * inv.y, by = sy * inv.y;
+            const float az = (pe.z - o.z) * inv.z, bz = sz * inv.z;
+            const uint32_t nx = inv.x >= 0.0f ? qa.x : qa.w, fx = inv.x >= 0.0f ? qa.w : qa.x;
+            const uint32_t ny = inv.y >= 0.0f ? qa.y : qb.x, fy = inv.y >= 0.0f ? qb.x : qa.y;
+            const uint32_t nz = inv.z >= 0.0f ? qa.z : qb.y, fz = inv.z >= 0.0f ? qb.y : qa.z;
             float key[4];
-            uint32_t r[4] = {RC[12], RC[13], RC[14], RC[15]};
+            uint32_t r[4] = {ch.x, ch.y, ch.z, ch.w};
             uint32_t nh = 0u;
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
@@ -993,22 +987,7 @@ __device__ __forceinline__ bool shadow_wave_q(const KArgs& A, f3 o, f3 d, f3 inv
             }
             if (nh != 0u) {
                 // entered children nearest first (by the first walking lane's entry distance)
-#define TRT_CSWAP(a, b)                                   \
-    do {                                                  \
-        const bool sw = key[b] < key[a];                  \
-        const float ta = key[a], tb = key[b];             \
-        const uint32_t ra = r[a], rb = r[b];              \
-        key[a] = sw ? tb : ta;                            \
-        key[b] = sw ? ta : tb;                            \
-        r[a] = sw ? rb : ra;                              \
-        r[b] = sw ? ra : rb;                              \
-    } while (0)
-                TRT_CSWAP(0, 1);
-                TRT_CSWAP(2, 3);
-                TRT_CSWAP(0, 2);
-                TRT_CSWAP(1, 3);
-                TRT_CSWAP(1, 2);
-#undef TRT_CSWAP
+                sort4(key, r);
 #pragma unroll
                 for (int k = 3; k >= 1; --k)
                     if ((uint32_t)k < nh) {
@@ -1020,8 +999,8 @@ __device__ __forceinline__ bool shadow_wave_q(const KArgs& A, f3 o, f3 d, f3 inv
                 continue;
             }
         } else {
-            const uint32_t first = node & kBvhFirstMask;
-            const uint32_t n = ((node >> kBvhCountShift) & 15u) + 1u;
+            uint32_t first, n;
+            leaf_range(node, first, n);
             for (uint32_t k = first; k < first + n; ++k)
                 if (shadow_tri_s(A, k, o, d, max_dist)) return true; // bvh_leaf's test, term for term
         }
@@ -1029,6 +1008,22 @@ __device__ __forceinline__ bool shadow_wave_q(const KArgs& A, f3 o, f3 d, f3 inv
         --sp;
         node = __builtin_amdgcn_readfirstlane(ws[sp]);
     }
+}
+
+// The floor (shader.comp:302-320): the plane y = -4 over |x| < 10, -30 < z < -5.  A hit in
+// (MIN_EPSILON, tmax) sets t.
+__device__ __forceinline__ bool floor_hit(f3 o, f3 d, float tmax, float& t) {
+    if (fabsf(d.y) > TRT_EPS) {
+        const float tp = div_rn(-(o.y + 4.0f), d.y);
+        if (tp > TRT_EPS && tp < tmax) {
+            const f3 p = add(o, muls(d, tp));
+            if (fabsf(p.x) < 10.0f && p.z < -5.0f && p.z > -30.0f) {
+                t = tp;
+                return true;
+            }
+        }
+    }
+    return false;
 }
 
 template <bool COUNT, int GEOM>
@@ -1040,18 +1035,7 @@ __device__ __forceinline__ void scene_intersect(const KArgs& A, f3 o, f3 d, Hit&
     h.v = 0.0f;
     h.ni = 0;
     h.batch = 0;
-    if (A.flags & TRT_FLAG_FLOOR) { // shader.comp:302-320
-        if (fabsf(d.y) > TRT_EPS) {
-            float t = div_rn(-(o.y + 4.0f), d.y);
-            if (t > TRT_EPS && t < h.t) {
-                f3 p = add(o, muls(d, t));
-                if (fabsf(p.x) < 10.0f && p.z < -5.0f && p.z > -30.0f) {
-                    h.t = t;
-                    h.kind = HIT_FLOOR;
-                }
-            }
-        }
-    }
+    if ((A.flags & TRT_FLAG_FLOOR) && floor_hit(o, d, h.t, h.t)) h.kind = HIT_FLOOR;
     if (A.flags & TRT_FLAG_SPHERES) { // shader.comp:322-335
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
@@ -2648,6 +2632,13 @@ __device__ __forceinline__ uint32_t inter_tile(const KArgs& A, uint32_t vb, uint
 #ifndef TRT_MESH_PAIRS
 #define TRT_MESH_PAIRS 0
 #endif
+// Whether a plain launch of more than one frame deals its blocks as frame pairs: one definition
+// for the host's grid size (launch_trace: half the blocks) and the kernel's dealing (trace_body,
+// with its GEOM).  Triangle-free frames only unless TRT_MESH_PAIRS: mesh kernels do not compile
+// the pair path.
+__host__ __device__ __forceinline__ bool pairs_launch(const KArgs& A, int geom) {
+    return A.xcd_inter && A.frame_group > 1u && (geom == 0 || TRT_MESH_PAIRS);
+}
 
 __device__ __forceinline__ void flush_counts(const KArgs& A, const Cnt& cnt) {
     const uint32_t v[20] = {cnt.pri, cnt.sec, cnt.sh, cnt.miss, cnt.trin, cnt.sph, cnt.bt, cnt.bh, cnt.tt, cnt.nt,
@@ -2724,7 +2715,7 @@ __device__ __forceinline__ void trace_body(const KArgs& A) {
     if (!SPLIT && !DEFER && A.nframes > 1u) {
         // frame pairs serve triangle-free frames only (the host sets frame_group 2 for them by
         // default): mesh kernels do not compile the two extra trace_tile copies (code size)
-        if (A.xcd_inter && A.frame_group > 1u && (GEOM == 0 || TRT_MESH_PAIRS)) {
+        if (pairs_launch(A, GEOM)) {
             // frame pairs: the block traces its tile in frames 2p and 2p + 1 (consecutive frames'
             // tiles cost nearly the same, so the pairs keep the waves balanced) — half the
             // workgroups, so half the per-workgroup launch and slot-refill overhead.  Two calls,
@@ -2911,6 +2902,9 @@ __global__ __launch_bounds__(64, waves_per_simd<GEOM>()) void trace_tasks(KArgs 
             Seg root{mk(0.0f, 0.0f, 0.0f), mk(0.0f, 0.0f, 0.0f), 0.0f, 0};
             uint32_t pixel = 0, link = kEvRoot;
             if (valid) {
+                // the task decode, once more in the plain branch below: one load_task() for both, in
+                // any form tried (out-parameter, struct by value), changed the triangle-free
+                // trace_tasks<0, false, 0, true> (tools/kres.py --diff class (b)), so the copies stay
                 const float4* q = reinterpret_cast<const float4*>(A.q_in + t);
                 const float4 a = q[0], b = q[1];
                 const uint32_t pd = __float_as_uint(b.w);
@@ -3183,16 +3177,32 @@ __global__ __launch_bounds__(64, waves_per_simd<GEOM>()) void shadow_batch_kerne
     occ[i] = shadow_intersect<false, GEOM>(A, mk(a.x, a.y, a.z), mk(b.x, b.y, b.z), a.w, cnt, slab) ? 1u : 0u;
 }
 
+// The geometry path of a launch, one choice for every launcher: 0 no triangles, 1 the
+// reference-order batch walk, 2 the per-lane BVH walk, 3 its 4-waves-per-SIMD build.
+static int geom_of(const KArgs& A) {
+    return A.nbatch == 0 ? 0 : (A.bvh && !(A.flags & TRT_FLAG_BATCH_WALK)) ? (A.bvh_waves4 ? 3 : 2) : 1;
+}
+// The run-time geometry path picks a template argument: f is a generic lambda, called with an
+// integral constant whose value (decltype(g)::value) is GEOM.  The launchers' CAP ladders
+// hand their capacity to a lambda the same way.
+template <int V>
+using ic = std::integral_constant<int, V>;
+template <typename F>
+static void dispatch_geom(int geom, F&& f) {
+    if (geom == 0) f(ic<0>{});
+    else if (geom == 1) f(ic<1>{});
+    else if (geom == 2) f(ic<2>{});
+    else f(ic<3>{});
+}
+
 hipError_t launch_shadow_batch(const KArgs& A0, const float4* rays, uint32_t n, uint32_t* occ, hipStream_t stream) {
     KArgs A = A0;
     A.diag = nullptr;
-    const int geom = A.nbatch == 0 ? 0 : (A.bvh && !(A.flags & TRT_FLAG_BATCH_WALK)) ? (A.bvh_waves4 ? 3 : 2) : 1;
     const dim3 grid((n + 63u) / 64u), block(64);
     if (!n) return hipSuccess;
-    if (geom == 0) hipLaunchKernelGGL(shadow_batch_kernel<0>, grid, block, 0, stream, A, rays, n, occ);
-    else if (geom == 1) hipLaunchKernelGGL(shadow_batch_kernel<1>, grid, block, 0, stream, A, rays, n, occ);
-    else if (geom == 2) hipLaunchKernelGGL(shadow_batch_kernel<2>, grid, block, 0, stream, A, rays, n, occ);
-    else hipLaunchKernelGGL(shadow_batch_kernel<3>, grid, block, 0, stream, A, rays, n, occ);
+    dispatch_geom(geom_of(A), [&](auto g) {
+        hipLaunchKernelGGL(shadow_batch_kernel<decltype(g)::value>, grid, block, 0, stream, A, rays, n, occ);
+    });
     return hipGetLastError();
 }
 
@@ -3278,12 +3288,9 @@ hipError_t launch_ray_query(const KArgs& A0, const float4* rays, uint32_t n, uin
     if (!n) return hipSuccess;
     KArgs A = A0;
     A.diag = nullptr;
-    // the geometry path exactly as launch_trace chooses it
-    const int geom = A.nbatch == 0 ? 0 : (A.bvh && !(A.flags & TRT_FLAG_BATCH_WALK)) ? (A.bvh_waves4 ? 3 : 2) : 1;
-    if (geom == 0) launch_query_g<0>(A, rays, n, out8, out32, hits, count, stream);
-    else if (geom == 1) launch_query_g<1>(A, rays, n, out8, out32, hits, count, stream);
-    else if (geom == 2) launch_query_g<2>(A, rays, n, out8, out32, hits, count, stream);
-    else launch_query_g<3>(A, rays, n, out8, out32, hits, count, stream);
+    dispatch_geom(geom_of(A), [&](auto g) {
+        launch_query_g<decltype(g)::value>(A, rays, n, out8, out32, hits, count, stream);
+    });
     return hipGetLastError();
 }
 #endif
@@ -3314,13 +3321,8 @@ __global__ __launch_bounds__(64, waves_per_simd<GEOM>()) void occlusion_query_ke
         const f3 d = normalize3(mk(b.x, b.y, b.z)); // shader.comp:593
         bool occ = false;
         if (A.flags & TRT_FLAG_FLOOR) { // scene_intersect's floor test with tmax for the nearest (tmax <= 1e10)
-            if (fabsf(d.y) > TRT_EPS) {
-                const float t = div_rn(-(o.y + 4.0f), d.y);
-                if (t > TRT_EPS && t < tmax) {
-                    const f3 p = add(o, muls(d, t));
-                    occ = fabsf(p.x) < 10.0f && p.z < -5.0f && p.z > -30.0f;
-                }
-            }
+            float tfloor;
+            occ = floor_hit(o, d, tmax, tfloor);
         }
         if (!occ) {
             Cnt cnt;
@@ -3336,13 +3338,10 @@ hipError_t launch_occlusion_query(const KArgs& A0, const float4* segs, uint32_t 
     if (!n) return hipSuccess;
     KArgs A = A0;
     A.diag = nullptr;
-    // the geometry path exactly as launch_ray_query chooses it
-    const int geom = A.nbatch == 0 ? 0 : (A.bvh && !(A.flags & TRT_FLAG_BATCH_WALK)) ? (A.bvh_waves4 ? 3 : 2) : 1;
     const dim3 grid((n + 63u) / 64u), block(64);
-    if (geom == 0) hipLaunchKernelGGL(occlusion_query_kernel<0>, grid, block, 0, stream, A, segs, n, out);
-    else if (geom == 1) hipLaunchKernelGGL(occlusion_query_kernel<1>, grid, block, 0, stream, A, segs, n, out);
-    else if (geom == 2) hipLaunchKernelGGL(occlusion_query_kernel<2>, grid, block, 0, stream, A, segs, n, out);
-    else hipLaunchKernelGGL(occlusion_query_kernel<3>, grid, block, 0, stream, A, segs, n, out);
+    dispatch_geom(geom_of(A), [&](auto g) {
+        hipLaunchKernelGGL(occlusion_query_kernel<decltype(g)::value>, grid, block, 0, stream, A, segs, n, out);
+    });
     return hipGetLastError();
 }
 #endif
@@ -3363,85 +3362,67 @@ hipError_t launch_trace(const KArgs& A, hipStream_t stream, bool) {
 hipError_t launch_trace(const KArgs& A, hipStream_t stream, bool count) {
     const uint32_t D = A.max_depth;
     const dim3 grid(A.ntiles), block(64);
-    const int geom = A.nbatch == 0 ? 0 : (A.bvh && !(A.flags & TRT_FLAG_BATCH_WALK)) ? (A.bvh_waves4 ? 3 : 2) : 1;
+    const int geom = geom_of(A);
     if (A.defer && !count && A.spp <= 1 && A.dctr && A.ev && A.shq && A.px_ev && A.fb) {
         hipError_t e = hipMemsetAsync(A.dctr, 0, sizeof(DeferCtr) * std::max(A.dframes, 1u), stream);
         if (e == hipSuccess && A.split_w >= 1 && A.ctr) e = hipMemsetAsync(A.ctr, 0, sizeof(SplitCtr), stream);
         if (e != hipSuccess) return e;
-#define TRT_DEFER_G(CAP, HYB)                                                \
-    do {                                                                     \
-        if (geom == 0) launch_defer<CAP, 0, HYB>(A, stream, grid, block);    \
-        else if (geom == 1) launch_defer<CAP, 1, HYB>(A, stream, grid, block); \
-        else if (geom == 2) launch_defer<CAP, 2, HYB>(A, stream, grid, block); \
-        else launch_defer<CAP, 3, HYB>(A, stream, grid, block);              \
-    } while (0)
-        // deep trees: TRT_DEFER_LDS deferred children in LDS + a private tail
-        if (D <= 1) TRT_DEFER_G(0, false);
-        else if (D <= 2) TRT_DEFER_G(1, false);
-        else if (D <= 3) TRT_DEFER_G(2, false);
-        else if (D <= 4) TRT_DEFER_G(3, false);
-        else TRT_DEFER_G(TRT_DEFER_LDS, true);
-#undef TRT_DEFER_G
+        dispatch_geom(geom, [&](auto g) {
+            constexpr int G = decltype(g)::value;
+            // deep trees: TRT_DEFER_LDS deferred children in LDS + a private tail
+            if (D <= 1) launch_defer<0, G, false>(A, stream, grid, block);
+            else if (D <= 2) launch_defer<1, G, false>(A, stream, grid, block);
+            else if (D <= 3) launch_defer<2, G, false>(A, stream, grid, block);
+            else if (D <= 4) launch_defer<3, G, false>(A, stream, grid, block);
+            else launch_defer<TRT_DEFER_LDS, G, true>(A, stream, grid, block);
+        });
         return hipGetLastError();
     }
     if (A.split_w >= 2 && A.split_w <= 5 && A.split_w < D && A.spp <= 1 && A.acc && A.ctr) {
         hipError_t e = hipMemsetAsync(A.ctr, 0, sizeof(SplitCtr), stream);
         if (e != hipSuccess) return e;
-#define TRT_SPLIT_G(CAP, G)                                                 \
-    do {                                                                    \
-        if (count) launch_split<CAP, true, G>(A, stream, grid, block);            \
-        else launch_split<CAP, false, G>(A, stream, grid, block);                 \
-    } while (0)
-#define TRT_SPLIT(CAP)                            \
-    do {                                          \
-        if (geom == 0) TRT_SPLIT_G(CAP, 0);       \
-        else if (geom == 1) TRT_SPLIT_G(CAP, 1);  \
-        else if (geom == 2) TRT_SPLIT_G(CAP, 2);  \
-        else TRT_SPLIT_G(CAP, 3);                 \
-    } while (0)
-        switch (A.split_w) {
-        case 2: TRT_SPLIT(1); break;
-        case 3: TRT_SPLIT(2); break;
-        case 4: TRT_SPLIT(3); break;
-        default: TRT_SPLIT(4); break;
-        }
-#undef TRT_SPLIT
-#undef TRT_SPLIT_G
+        dispatch_geom(geom, [&](auto g) {
+            constexpr int G = decltype(g)::value;
+            auto split = [&](auto cap) {
+                constexpr int CAP = decltype(cap)::value;
+                if (count) launch_split<CAP, true, G>(A, stream, grid, block);
+                else launch_split<CAP, false, G>(A, stream, grid, block);
+            };
+            switch (A.split_w) {
+            case 2: split(ic<1>{}); break;
+            case 3: split(ic<2>{}); break;
+            case 4: split(ic<3>{}); break;
+            default: split(ic<4>{}); break;
+            }
+        });
         return hipGetLastError();
     }
     // a plain launch traces A.nframes frames: ntiles blocks per frame (frame-major)
     const uint32_t fblocks = A.spp_lanes ? std::max(A.nframes, 1u) * A.spp
-                             : A.nframes > 1u && A.xcd_inter && A.frame_group > 1u && (geom == 0 || TRT_MESH_PAIRS)
-                                 ? (A.nframes + 1u) / 2u
-                                 : std::max(A.nframes, 1u);
+                             : A.nframes > 1u && pairs_launch(A, geom) ? (A.nframes + 1u) / 2u
+                                                                       : std::max(A.nframes, 1u);
     const dim3 fgrid(A.ntiles * fblocks);
     // the sky table's kernel: what the host's conditions (attach_sky) promise, checked again
     const bool sky = A.sky && geom == 0 && !count && A.spp <= 1 && !A.rays_in && !A.out32;
-#define TRT_LAUNCH_G(CAP, G)                                                                             \
-    do {                                                                                                 \
-        if (count) hipLaunchKernelGGL((trace_kernel<CAP, true, G, false>), fgrid, block, 0, stream, A);  \
-        else if (G == 0 && sky && A.span_tables && A.smask && A.floor_class) hipLaunchKernelGGL((sky_trace_kernel_floor<CAP>), fgrid, block, 0, stream, A); \
-        else if (G == 0 && sky && A.span_tables && A.smask) hipLaunchKernelGGL((sky_trace_kernel_smask<CAP>), fgrid, block, 0, stream, A); \
-        else if (G == 0 && sky && A.span_tables) hipLaunchKernelGGL((sky_trace_kernel<CAP>), fgrid, block, 0, stream, A); \
-        else if (G == 0 && sky) hipLaunchKernelGGL((sky_trace_kernel_nospan<CAP>), fgrid, block, 0, stream, A); \
-        else hipLaunchKernelGGL((trace_kernel<CAP, false, G, false>), fgrid, block, 0, stream, A);       \
-    } while (0)
-#define TRT_LAUNCH(CAP)                          \
-    do {                                         \
-        if (geom == 0) TRT_LAUNCH_G(CAP, 0);     \
-        else if (geom == 1) TRT_LAUNCH_G(CAP, 1); \
-        else if (geom == 2) TRT_LAUNCH_G(CAP, 2); \
-        else TRT_LAUNCH_G(CAP, 3);               \
-    } while (0)
-    if (D <= 1) TRT_LAUNCH(0);
-    else if (D <= 2) TRT_LAUNCH(1);
-    else if (D <= 3) TRT_LAUNCH(2);
-    else if (D <= 4) TRT_LAUNCH(3);
-    else if (D <= 5) TRT_LAUNCH(4);
-    else if (D <= 8) TRT_LAUNCH(7);
-    else TRT_LAUNCH(19);
-#undef TRT_LAUNCH
-#undef TRT_LAUNCH_G
+    dispatch_geom(geom, [&](auto g) {
+        constexpr int G = decltype(g)::value;
+        auto launch = [&](auto cap) {
+            constexpr int CAP = decltype(cap)::value;
+            if (count) hipLaunchKernelGGL((trace_kernel<CAP, true, G, false>), fgrid, block, 0, stream, A);
+            else if (G == 0 && sky && A.span_tables && A.smask && A.floor_class) hipLaunchKernelGGL((sky_trace_kernel_floor<CAP>), fgrid, block, 0, stream, A);
+            else if (G == 0 && sky && A.span_tables && A.smask) hipLaunchKernelGGL((sky_trace_kernel_smask<CAP>), fgrid, block, 0, stream, A);
+            else if (G == 0 && sky && A.span_tables) hipLaunchKernelGGL((sky_trace_kernel<CAP>), fgrid, block, 0, stream, A);
+            else if (G == 0 && sky) hipLaunchKernelGGL((sky_trace_kernel_nospan<CAP>), fgrid, block, 0, stream, A);
+            else hipLaunchKernelGGL((trace_kernel<CAP, false, G, false>), fgrid, block, 0, stream, A);
+        };
+        if (D <= 1) launch(ic<0>{});
+        else if (D <= 2) launch(ic<1>{});
+        else if (D <= 3) launch(ic<2>{});
+        else if (D <= 4) launch(ic<3>{});
+        else if (D <= 5) launch(ic<4>{});
+        else if (D <= 8) launch(ic<7>{});
+        else launch(ic<19>{});
+    });
     return hipGetLastError();
 }
 #endif
