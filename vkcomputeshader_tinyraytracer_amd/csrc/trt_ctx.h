@@ -67,6 +67,7 @@ struct trt_ctx {
     // masks.  floor_on: the TRT_FLOOR_CLASS env knob; sph_span: the sphere intervals of the launch
     // being prepared (fill_spans writes them, attach_floor_class packs them into KArgs::span).
     bool floor_on = true;
+    bool floor_lit_on = true; // the TRT_FLOOR_LIT env knob (KArgs::floor_class kFloorLit)
     uint32_t sph_span[trt::kSpanWords] = {};
     // Shadow occluder masks (KArgs::smask, shadow_mask.h) of every launch that has sky spans:
     // d_smask holds the floor cells of smask_key's scene, rebuilt when the bytes the build reads

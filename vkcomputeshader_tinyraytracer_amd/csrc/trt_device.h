@@ -286,11 +286,15 @@ struct KArgs {
     uint32_t smask_rows[2];
     // Floor class (sky_trace_kernel_floor only; needs span_tables, smask, ntx <= 255, nframes >= 2): `span`
     // holds floor_pack words, c0 | c1 << 8 | s0 << 16 | s1 << 24 — a tile inside [c0, c1) and
-    // outside the sphere interval [s0, s1) can only hit the floor.  0: `span` as above.
+    // outside the sphere interval [s0, s1) can only hit the floor.  0: `span` as above.  With
+    // kFloorLit beside bit 0 the launch runs sky_trace_kernel_floor_lit: the floor is grey (no
+    // checker) and every light lies above its plane by more than kFloorLitPad (attach_floor_class).
     uint32_t floor_class;
     uint32_t view_on;
 };
-static_assert(sizeof(float) * 9 * kMaxViewFrames <= sizeof(uint32_t) * kSpanWords, "the view bases fit the spans' bytes");
+constexpr uint32_t kFloorLit = 2u;     // KArgs::floor_class
+constexpr float kFloorLitPad = 1e-2f; // the shadow masks' pad above the floor plane y = -4
+static_assert(sizeof(float) * 9 * kMaxViewFrames <=sizeof(uint32_t) * kSpanWords, "the view bases fit the spans' bytes");
 static_assert(sizeof(KArgs) <= 4096, "KArgs fits the 4 KB kernel-argument limit");
 
 } // namespace trt

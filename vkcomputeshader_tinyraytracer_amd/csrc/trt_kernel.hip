@@ -2259,6 +2259,21 @@ __device__ __forceinline__ void store_pixel(const KArgs& A, const FrameRec& F, s
     if (F.out8) F.out8[o] = pack_rgba8(A, g);
 }
 
+// store_pixel of a grey colour (c, c, c), `c` clamped: one gamma, one sRGB encode and one rounded
+// byte in place of three of each on equal bits, so the same words (floor_frame LIT).
+__device__ __forceinline__ void store_pixel_grey(const KArgs& A, const FrameRec& F, size_t o, float c) {
+    o = out_index(A, F, o);
+    const float g = pow_pos(c, TRT_GAMMA);
+#ifndef TRT_DIAG_WAVE_CLOCK
+    if (A.out32) reinterpret_cast<float4*>(A.out32)[o] = make_float4(g, g, g, 1.0f);
+#endif
+    if (F.out8) {
+        const float e = (A.flags & TRT_FLAG_SRGB_OUT) ? srgb_encode(g) : g;
+        const uint32_t r = (uint32_t)floorf(e * 255.0f + 0.5f);
+        F.out8[o] = r | (r << 8) | (r << 16) | (255u << 24);
+    }
+}
+
 // Sky spans (KArgs::span, sky_spans.h): the span word of `tile` in frame f of the launch.  Both
 // are wave-uniform, so this is scalar work and one scalar load from the kernel arguments.
 __device__ __forceinline__ uint32_t span_word(const KArgs& A, uint32_t tile, uint32_t f) {
@@ -2302,6 +2317,11 @@ __device__ __forceinline__ bool floor_sphere_outside(uint32_t col, uint32_t w) {
 // floor hit never uses: scene_intersect's floor test alone, then cast_seg's HIT_FLOOR branch with
 // alb = {2, 0, 0, 0} (no specular term, no children, so no loop and no stack).  A lane that
 // misses is a primary miss: its pixel is its sky-table word.
+// LIT (sky_trace_kernel_floor_lit; the host's floor_lit conditions, attach_floor_class: no checker,
+// every light above the floor plane by more than 1e-2): kd is (0.3, 0.3, 0.3), so the three
+// channels are one value through the same operations in the same order, and a wave none of whose
+// floor lanes has a mask bit shades without the shadow set-up (DESIGN.md 4.27 has the proof).
+template <bool LIT>
 __device__ __forceinline__ void floor_frame(const KArgs& A, const FrameRec& F, f3 d, uint32_t word, size_t o, Cnt& cnt,
                                             float4* slab) {
     const f3 orig = mk(F.cam[0], F.cam[1], F.cam[2]);
@@ -2331,6 +2351,43 @@ __device__ __forceinline__ void floor_frame(const KArgs& A, const FrameRec& F, f
     sm = 0u;
 #endif
     const f3 n = mk(0.0f, 1.0f, 0.0f);
+    if constexpr (LIT) {
+        const float kd = 0.3f, alb0 = 2.0f, alb1 = 0.0f, specular = 0.0f;
+        float diffuse = 0.0f;
+        // normalize_len3's terms of the three lights, which both branches need, before the branch:
+        // the wave-uniform test waits for the mask cell's load, and these are the work that hides it
+        static_assert(TRT_FUSED_NLEN, "the terms below are normalize_len3's fused form");
+        f3 v[3];
+        float inv[3], dist[3];
+#pragma unroll
+        for (int i = 0; i < 3; ++i) {
+            v[i] = sub(mk(A.light[i][0], A.light[i][1], A.light[i][2]), p);
+            dist[i] = sqrt_rsqrt_rn(dot3(v[i], v[i]), inv[i]);
+        }
+        if (__ballot(sm != 0u) == 0ull) {
+            // no query of this wave is traced (shadow_intersect's first ballot, light by light), and
+            // dot3(n, ld) = (0 * ld.x + 1 * ld.y) + 0 * ld.z is ld.y = v.y * inv > 0 bit for bit
+#pragma unroll
+            for (int i = 0; i < 3; ++i) {
+                const float diff = 1.0f * fmaxf(0.0f, v[i].y * inv[i]);
+                diffuse = diffuse + kd * diff; // diff > 0: the light matters
+            }
+        } else {
+#pragma unroll
+            for (int i = 0; i < 3; ++i) {
+                const f3 ld = muls(v[i], inv[i]); // normalize_len3
+                const f3 so = dot3(ld, n) < 0.0f ? sub(p, muls(n, TRT_EPS)) : add(p, muls(n, TRT_EPS));
+                const float diff = 1.0f * fmaxf(0.0f, dot3(n, ld));
+                const bool matters = TRT_SKIP_DARK == 0 || diff != 0.0f;
+                if (!matters) continue;
+                if (shadow_intersect<false, 0, true>(A, so, ld, dist[i], cnt, slab, sm >> (4 * i))) continue;
+                diffuse = diffuse + kd * diff;
+            }
+        }
+        const float c = 0.0f + ((diffuse * alb0 + specular * alb1) * 1.0f);
+        store_pixel_grey(A, F, o, clamp01(c));
+        return;
+    }
     float c1 = 0.3f, c2 = 0.3f;
     if (A.flags & TRT_FLAG_CHECKER) { // shader.comp:312
         const float m = floorf(p.x * 0.5f + 1024.0f) + floorf(p.z * 0.5f);
@@ -2366,6 +2423,7 @@ __device__ __forceinline__ void floor_frame(const KArgs& A, const FrameRec& F, f
 // the same in both frames) and the sky word once per wave.  One floor_frame body in a rolled loop:
 // the body is short and far from the register cap, so what the loop hoists costs nothing, and the
 // second copy was 11 KB of the kernel's code.
+template <bool LIT>
 __device__ __forceinline__ void floor_tile(const KArgs& A, uint32_t tile, uint32_t f, uint32_t nf, Cnt& cnt, float4* slab) {
     const uint32_t lane = lane_id();
     const uint32_t x = (tile % A.ntx) * 8u + (lane & 7u), k = (tile / A.ntx) * 8u + (lane >> 3);
@@ -2375,7 +2433,7 @@ __device__ __forceinline__ void floor_tile(const KArgs& A, uint32_t tile, uint32
     const f3 d = primary_dir<false>(A, x, y, 0);
     const uint32_t word = A.sky[(size_t)y * A.width + x];
 #pragma nounroll
-    for (uint32_t j = 0; j < nf; ++j) floor_frame(A, A.fr[f + j], d, word, o, cnt, slab);
+    for (uint32_t j = 0; j < nf; ++j) floor_frame<LIT>(A, A.fr[f + j], d, word, o, cnt, slab);
 }
 
 // One 8x8 pixel tile of compact output rows: the wave's 64 lanes, one pixel each.  SPLIT
@@ -2677,11 +2735,12 @@ constexpr int trace_waves() {
 }
 
 template <int CAP, bool COUNT, int GEOM, bool SPLIT, bool DEFER, bool HYB, bool SKY, bool SPANS = false,
-          bool SMASK = false, bool FLOORC = false>
+          bool SMASK = false, bool FLOORC = false, bool FLOORLIT = false>
 __device__ __forceinline__ void trace_body(const KArgs& A) {
     static_assert(!SPANS || SKY, "the sky spans cull into the sky table");
     static_assert(!SMASK || SPANS, "the occluder masks ride on the span kernel");
     static_assert(!FLOORC || SMASK, "the floor class rides on the mask kernel");
+    static_assert(!FLOORLIT || FLOORC, "the lit floor is the floor class's");
     __shared__ float lds[DEFER ? defer_pool_floats() : lds_stack_floats<CAP, GEOM, HYB>()];
     // GEOM 1: one batch slab, 64 x (v0, e1, e2); GEOM 2: the BVH traversal stacks
     __shared__ float4 slab[slab_float4s<GEOM>()];
@@ -2801,7 +2860,7 @@ __device__ __forceinline__ void trace_body(const KArgs& A) {
 #ifdef TRT_DIAG_FLOOR_SKY
             sky_tile_store(A, tile, A.fr[f], nf > 1u ? &A.fr[f + 1u] : nullptr);
 #else
-            floor_tile(A, tile, f, nf, cnt, slab);
+            floor_tile<FLOORLIT>(A, tile, f, nf, cnt, slab);
 #endif
             return;
         }
@@ -2877,6 +2936,15 @@ __global__ __launch_bounds__(64, (trace_waves<0, CAP, false, false>())) void sky
 template <int CAP>
 __global__ __launch_bounds__(64, (trace_waves<0, CAP, false, false>())) void sky_trace_kernel_floor(KArgs A) {
     trace_body<CAP, false, 0, false, false, false, true, true, true, true>(A);
+}
+
+// sky_trace_kernel_floor for a launch whose floor is grey and lit from above (A.floor_class &
+// kFloorLit: floor_frame LIT).  A kernel of its own once more: a launch without the flag
+// (TRT_FLOOR_LIT=0, the checker floor, a light at or below the floor plane) runs
+// sky_trace_kernel_floor exactly as before.
+template <int CAP>
+__global__ __launch_bounds__(64, (trace_waves<0, CAP, false, false>())) void sky_trace_kernel_floor_lit(KArgs A) {
+    trace_body<CAP, false, 0, false, false, false, true, true, true, true, true>(A);
 }
 
 // One round of a split frame: persistent waves take 64 tasks at a time (static schedule) from
@@ -3409,6 +3477,7 @@ hipError_t launch_trace(const KArgs& A, hipStream_t stream, bool count) {
         auto launch = [&](auto cap) {
             constexpr int CAP = decltype(cap)::value;
             if (count) hipLaunchKernelGGL((trace_kernel<CAP, true, G, false>), fgrid, block, 0, stream, A);
+            else if (G == 0 && sky && A.span_tables && A.smask && (A.floor_class & kFloorLit)) hipLaunchKernelGGL((sky_trace_kernel_floor_lit<CAP>), fgrid, block, 0, stream, A);
             else if (G == 0 && sky && A.span_tables && A.smask && A.floor_class) hipLaunchKernelGGL((sky_trace_kernel_floor<CAP>), fgrid, block, 0, stream, A);
             else if (G == 0 && sky && A.span_tables && A.smask) hipLaunchKernelGGL((sky_trace_kernel_smask<CAP>), fgrid, block, 0, stream, A);
             else if (G == 0 && sky && A.span_tables) hipLaunchKernelGGL((sky_trace_kernel<CAP>), fgrid, block, 0, stream, A);

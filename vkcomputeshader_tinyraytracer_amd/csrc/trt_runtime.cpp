@@ -368,6 +368,7 @@ int trt_create(trt_ctx** out, int hip_device) {
     if (const char* e = std::getenv("TRT_SKY_SPAN_FRAMES")) c->span_frames = (uint32_t)std::min(64, std::max(0, std::atoi(e)));
     if (const char* e = std::getenv("TRT_SHADOW_MASK")) c->smask_on = std::atoi(e) != 0;
     if (const char* e = std::getenv("TRT_FLOOR_CLASS")) c->floor_on = std::atoi(e) != 0;
+    if (const char* e = std::getenv("TRT_FLOOR_LIT")) c->floor_lit_on = std::atoi(e) != 0;
     if (const char* e = std::getenv("TRT_SHADOW_MASK_CELL")) { // floor cell edge; the build clamps it
         const float v = (float)std::atof(e);
         if (v > 0.0f) c->smask_cell = v;
@@ -878,6 +879,17 @@ int attach_smask(trt_ctx* c, KArgs& A, hipStream_t stream) {
 // TRT_FLOOR_CLASS=0, keeps its span words and runs the kernel it ran before.  So does a launch of
 // one frame: frames launched one by one were 1.5-2.2 % slower with the class than without
 // (profiles/floor_class_ab_summary.txt), so they neither compute the intervals nor change kernel.
+//
+// floor_lit (kFloorLit beside the class bit, sky_trace_kernel_floor_lit): the floor's three
+// channels are one value and every light shines on its upper side, which floor_frame LIT relies on.
+// Not under TRT_FLOOR_LIT=0: the launch then runs sky_trace_kernel_floor as before.
+uint32_t floor_lit(uint32_t flags, const float (*light)[3]) {
+    if (flags & TRT_FLAG_CHECKER) return 0u;
+    for (int i = 0; i < 3; ++i)
+        if (!(light[i][1] + 4.0f > trt::kFloorLitPad)) return 0u; // NaN too
+    return 1u;
+}
+
 void attach_floor_class(const trt_ctx* c, KArgs& A) {
     A.floor_class = 0;
     if (!c->floor_on || A.nframes < 2u || !A.span_tables || !A.smask || A.ntx > trt::kFloorPackMaxNtx) return;
@@ -885,6 +897,7 @@ void attach_floor_class(const trt_ctx* c, KArgs& A) {
     const uint32_t words = A.span_tables * A.span_ntr;
     for (uint32_t i = 0; i < words; ++i) A.span[i] = trt::floor_pack(A.span[i], c->sph_span[i]);
     A.floor_class = 1;
+    if (c->floor_lit_on && floor_lit(A.flags, A.light)) A.floor_class |= trt::kFloorLit;
 }
 
 int check_params(trt_ctx* c, const trt_params* p) {
@@ -1895,6 +1908,13 @@ extern "C" int trt_diag_set_buffer(trt_ctx* c, void* dev_ptr) {
     if (!c) return TRT_ERR_INVALID;
     c->diag = dev_ptr;
     return TRT_OK;
+}
+
+// attach_floor_class's floor_lit conditions on a launch's flags and its three lights (x, y, z
+// each), without the knob: 1 or 0 (tests/test_floor_lit.py, no GPU).
+extern "C" int trt_diag_floor_lit(uint32_t flags, const float* lights) {
+    if (!lights) return 0;
+    return (int)floor_lit(flags, reinterpret_cast<const float(*)[3]>(lights));
 }
 
 // counters[k] of the last counting pass (k < 32).
