@@ -10,7 +10,10 @@ mkdir -p "$OUT" "$ROOT/build/diag"
 FP=$(make -s -C "$SRC" print-kernel-flags)
 HOST="-O2 -std=c++17 -fPIC -ffp-contract=off -I/opt/rocm/include -D__HIP_PLATFORM_AMD__"
 HDR_NEWEST=$(ls -t "$SRC"/*.h "$ROOT"/include/trt/*.h | head -n 1)
-for f in trt_runtime sky_spans shadow_mask trt_multi band_plan scene_build obj_load bvh_build image_io jpeg_entropy jpeg_api; do
+# the host sources: one list, the Makefile's
+HOST_OBJS=()
+for f in $(make -s -C "$SRC" print-host-sources); do
+    HOST_OBJS+=("$ROOT/build/diag/$f.o")
     [ "$ROOT/build/diag/$f.o" -nt "$SRC/$f.cpp" ] && [ "$ROOT/build/diag/$f.o" -nt "$HDR_NEWEST" ] || /opt/rocm/bin/hipcc $HOST -x c++ -c -o "$ROOT/build/diag/$f.o" "$SRC/$f.cpp"
 done
 variant() { # name extra-flags...
@@ -19,9 +22,7 @@ variant() { # name extra-flags...
     /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC $FP "$@" -c -o "$ROOT/build/diag/k_$name.o" "${KSRC:-$SRC/trt_kernel.hip}"
     [ "$ROOT/build/diag/jpeg_kernel.o" -nt "$SRC/jpeg_kernel.hip" ] || /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC $FP -c -o "$ROOT/build/diag/jpeg_kernel.o" "$SRC/jpeg_kernel.hip"
     /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o "$OUT/libtrt_$name.so" "$ROOT/build/diag/k_$name.o" \
-        "$ROOT/build/diag/trt_runtime.o" "$ROOT/build/diag/sky_spans.o" "$ROOT/build/diag/shadow_mask.o" "$ROOT/build/diag/trt_multi.o" "$ROOT/build/diag/band_plan.o" "$ROOT/build/diag/scene_build.o" "$ROOT/build/diag/obj_load.o" \
-        "$ROOT/build/diag/bvh_build.o" "$ROOT/build/diag/image_io.o" "$ROOT/build/diag/jpeg_entropy.o" \
-        "$ROOT/build/diag/jpeg_api.o" "$ROOT/build/diag/jpeg_kernel.o" -lz -L/opt/rocm/lib -lrccl -Wl,-rpath,/opt/rocm/lib
+        "${HOST_OBJS[@]}" "$ROOT/build/diag/jpeg_kernel.o" -lz -L/opt/rocm/lib -lrccl -Wl,-rpath,/opt/rocm/lib
     echo "built $OUT/libtrt_$name.so"
 }
 for v in "$@"; do

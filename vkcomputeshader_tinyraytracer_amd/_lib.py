@@ -138,6 +138,8 @@ def lib() -> ctypes.CDLL:
                                   ctypes.POINTER(c_u32)]),
         "trt_diag_shadow_mask": (c_int, [f3, f3, c_u32, ctypes.c_float, ctypes.POINTER(ctypes.c_uint16), c_u32,
                                          ctypes.POINTER(c_u32), ctypes.POINTER(c_u32), ctypes.POINTER(c_u32)]),
+        # not in abi.h: the host packing of a scene, hashed (csrc/trt_diag.cpp, tests/test_scene_pack.py)
+        "trt_diag_scene_pack": (c_int, [vp, c_u32, vp, c_u32, ctypes.POINTER(ctypes.c_uint64)]),
     }
     for name, (res, args) in sigs.items():
         fn = getattr(L, name)

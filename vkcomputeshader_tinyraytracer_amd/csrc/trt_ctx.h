@@ -1,7 +1,8 @@
 // trt_ctx.h — the context behind the C-ABI's opaque trt_ctx (internal to libtrt).
 //
-// Shared by trt_runtime.cpp (the single-GPU ABI) and trt_multi.cpp (the multi-GPU frame
-// tiling over RCCL, which broadcasts a context's scene bindings to the other devices).
+// Shared by the single-GPU ABI (trt_runtime.cpp, trt_scene_upload.cpp, trt_diag.cpp, through
+// trt_internal.h) and trt_multi.cpp (the multi-GPU frame tiling over RCCL, which broadcasts a
+// context's scene bindings to the other devices).
 #pragma once
 
 #include <hip/hip_runtime.h>

@@ -1,31 +1,25 @@
-// trt_runtime.cpp — the C-ABI (include/trt/abi.h) over the HIP runtime.
+// trt_runtime.cpp — the C-ABI (include/trt/abi.h) over the HIP runtime: the context's lifecycle,
+// the setters and the render and query entry points.
 //
 // Replaces the reference's Vulkan compute plumbing: createShaderStorageBuffers() /
 // createUniformBuffers() / the background texture upload (main.cpp:928-1111, 1494-1664)
-// become trt_upload_scene(); updateUniformBuffer() (main.cpp:2165-2179) becomes
-// trt_update_ubo(); recordComputeCommandBuffer() + vkQueueSubmit (main.cpp:2108-2131,
+// become trt_upload_scene() (trt_scene_upload.cpp); updateUniformBuffer() (main.cpp:2165-2179)
+// becomes trt_update_ubo(); recordComputeCommandBuffer() + vkQueueSubmit (main.cpp:2108-2131,
 // 2181-2205) become trt_render().  No exception crosses the ABI; failures set the context's
 // last error and return a negative TRT_ERR_* code (the reference throws std::runtime_error
 // and exits, main.cpp:2565-2573).
-#include <hip/hip_runtime.h>
-
 #include <algorithm>
 #include <cmath>
 #include <cstddef>
-#include <cstdio>
 #include <cstdlib>
-#include <limits>
 #include <cstring>
-#include <map>
 #include <new>
-#include <string>
 #include <vector>
 
-#include "../../include/trt/abi.h"
 #include "jpeg.h"
+#include "scene_pack.h"
 #include "trt_bands.h"
-#include "trt_ctx.h"
-#include "trt_device.h"
+#include "trt_internal.h"
 #include "trt_qray.h"
 
 namespace trt {
@@ -36,28 +30,6 @@ hipError_t touch_stream(hipStream_t s, void* scratch) {
     hipError_t e = hipMemsetAsync(scratch, 0, 4, s);
     return e == hipSuccess ? hipStreamSynchronize(s) : e;
 }
-hipError_t launch_trace(const KArgs& A, hipStream_t stream, bool count);
-hipError_t launch_envp(const uint32_t* env, uint2* out, uint32_t W, uint32_t H, hipStream_t stream);
-hipError_t launch_sky(const KArgs& A, uint32_t* out, hipStream_t stream);
-hipError_t launch_shadow_batch(const KArgs& A, const float4* rays, uint32_t n, uint32_t* occ, hipStream_t stream);
-hipError_t launch_ray_query(const KArgs& A, const float4* rays, uint32_t n, uint32_t* out8, float4* out32, uint4* hits,
-                            bool count, hipStream_t stream);
-hipError_t launch_occlusion_query(const KArgs& A, const float4* segs, uint32_t n, uint8_t* out, hipStream_t stream);
-uint32_t collapse_bvh4(const std::vector<BvhNode>& b2, std::vector<Bvh4Node>& b4);
-uint32_t bvh_depth(const std::vector<BvhNode>& b2);
-bool quantize_bvh4(const std::vector<Bvh4Node>& b4, std::vector<Bvh4QNode>& out);
-bool build_bvh(const trt_triangle* tris, uint32_t ntri, const trt_model* models, uint32_t nmodel,
-               std::vector<BvhNode>& nodes, std::vector<TriGeo>& leaf_tris);
-}
-
-using trt::BatchRec;
-using trt::KArgs;
-using trt::Mat;
-using trt::TriGeo;
-using trt::TriShade;
-
-
-namespace {
 
 int fail(trt_ctx* c, int code, const std::string& msg) {
     if (c) c->err = msg;
@@ -71,49 +43,6 @@ int hip_fail(trt_ctx* c, hipError_t e, const char* what) {
     return fail(c, e == hipErrorOutOfMemory ? TRT_ERR_OOM : TRT_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e));
 }
 
-// Failure injection (tests only, with TRT_ENABLE_TEST_HOOKS=1): TRT_TEST_FAIL_DEFER_SLOT=k makes
-// the deferred-frame scratch allocation of in-flight slot k report out-of-memory.
-int test_fail_defer_slot() {
-    const char* on = std::getenv("TRT_ENABLE_TEST_HOOKS");
-    const char* e = std::getenv("TRT_TEST_FAIL_DEFER_SLOT");
-    return (on && std::atoi(on) == 1 && e) ? std::atoi(e) : -1;
-}
-
-#define HIP_TRY(ctx, expr)                                       \
-    do {                                                         \
-        hipError_t e_ = (expr);                                  \
-        if (e_ != hipSuccess) return hip_fail((ctx), e_, #expr); \
-    } while (0)
-
-void free_scene(trt_ctx* c) {
-    (void)hipFree(c->d_batches);
-    (void)hipFree(c->d_nodes);
-    (void)hipFree(c->d_bvh);
-    (void)hipFree(c->d_bvh4);
-    (void)hipFree(c->d_bvh4q);
-    (void)hipFree(c->d_bvh_tris);
-    (void)hipFree(c->d_geo);
-    (void)hipFree(c->d_shade);
-    (void)hipFree(c->d_mats);
-    (void)hipFree(c->d_env);
-    c->d_batches = nullptr;
-    c->d_nodes = nullptr;
-    c->d_bvh = nullptr;
-    c->d_bvh4 = nullptr;
-    c->d_bvh4q = nullptr;
-    c->d_bvh_tris = nullptr;
-    c->top = 0;
-    c->d_geo = nullptr;
-    c->d_shade = nullptr;
-    c->d_mats = nullptr;
-    c->d_env = nullptr;
-    c->envp_ok = false;
-    ++c->env_gen;
-    c->nbatch = c->ntri = c->nmat = c->env_w = c->env_h = 0;
-    std::memset(c->scene_bytes, 0, sizeof(c->scene_bytes));
-    c->have_scene = false;
-}
-
 // Grow-only device scratch buffer.
 int ensure(trt_ctx* c, void** p, size_t* cap, size_t bytes, const char* what) {
     if (bytes <= *cap && *p) return TRT_OK;
@@ -125,42 +54,33 @@ int ensure(trt_ctx* c, void** p, size_t* cap, size_t bytes, const char* what) {
     *cap = bytes;
     return TRT_OK;
 }
+} // namespace trt
 
-Mat to_mat(const trt_material& m) {
-    Mat r{};
-    r.albedo[0] = m.albedo.x;
-    r.albedo[1] = m.albedo.y;
-    r.albedo[2] = m.albedo.z;
-    r.albedo[3] = m.albedo.w;
-    r.kd[0] = m.diffuse_specular.x;
-    r.kd[1] = m.diffuse_specular.y;
-    r.kd[2] = m.diffuse_specular.z;
-    r.spec_exp = m.diffuse_specular.w;
-    r.ior = m.refractive.x;
-    return r;
+using namespace trt;
+
+namespace {
+
+// Failure injection (tests only, with TRT_ENABLE_TEST_HOOKS=1): TRT_TEST_FAIL_DEFER_SLOT=k makes
+// the deferred-frame scratch allocation of in-flight slot k report out-of-memory.
+int test_fail_defer_slot() {
+    const char* on = std::getenv("TRT_ENABLE_TEST_HOOKS");
+    const char* e = std::getenv("TRT_TEST_FAIL_DEFER_SLOT");
+    return (on && std::atoi(on) == 1 && e) ? std::atoi(e) : -1;
 }
 
 void fill_ubo_args(KArgs& A, const trt_ubo& u) {
     const trt_sphere* s[4] = {&u.sphere0, &u.sphere1, &u.sphere2, &u.sphere3};
     for (int i = 0; i < 4; ++i) {
-        A.sph[i].c[0] = s[i]->center_radius.x;
-        A.sph[i].c[1] = s[i]->center_radius.y;
-        A.sph[i].c[2] = s[i]->center_radius.z;
+        std::memcpy(A.sph[i].c, &s[i]->center_radius, sizeof(A.sph[i].c)); // x, y, z
         A.sph[i].r = s[i]->center_radius.w;
         A.sph[i].m = to_mat(s[i]->material);
     }
     const trt_vec4* l[3] = {&u.light0, &u.light1, &u.light2};
-    for (int i = 0; i < 3; ++i) {
-        A.light[i][0] = l[i]->x;
-        A.light[i][1] = l[i]->y;
-        A.light[i][2] = l[i]->z;
-    }
+    for (int i = 0; i < 3; ++i) std::memcpy(A.light[i], l[i], sizeof(A.light[i])); // x, y, z
 }
 
 void fill_frame(trt::FrameRec& f, const trt_ubo& u, uint8_t* out8, bool in_place) {
-    f.cam[0] = u.camPos.x;
-    f.cam[1] = u.camPos.y;
-    f.cam[2] = u.camPos.z;
+    std::memcpy(f.cam, &u.camPos, sizeof(f.cam)); // x, y, z
     f.in_place = in_place ? 1u : 0u;
     f.out8 = reinterpret_cast<uint32_t*>(out8);
 }
@@ -181,10 +101,11 @@ void fill_view(KArgs& A, uint32_t f, const trt_view& v) {
     std::memcpy(A.view[f], &v, sizeof(trt_view));
 }
 
-// Steps 1 and 2 of the view contract (abi.h trt_view) for one pixel at spp 1: dir_z as fill_args
-// (main.cpp:1503); the rest is primary_dir's spp-1 arithmetic, operation for operation (this
-// file compiles with -ffp-contract=off).  Shared by trt_view_rays and trt_pixel_ray.
+// dir_z = -1.0 * (HEIGHT / (2.0 * tan(fov / 2.0))) in double, main.cpp:1503: the one expression
+// behind KArgs::dz (fill_args), trt_view_rays and trt_pixel_ray.
 float view_dz(const trt_params* p) { return (float)(-1.0 * ((double)p->height / (2.0 * std::tan((double)p->fov / 2.0)))); }
+// Steps 1 and 2 of the view contract (abi.h trt_view) for one pixel at spp 1: primary_dir's spp-1
+// arithmetic, operation for operation (this file compiles with -ffp-contract=off).
 void view_pixel_dir(const trt_params* p, const trt_view& V, float dz, uint32_t x, uint32_t y, float w[3]) {
     const uint32_t W = p->width, H = p->height;
     const uint32_t row = ((p->flags & TRT_FLAG_ROW_QUIRK) && x + 1u == W) ? y + 1u : y;
@@ -202,6 +123,51 @@ bool same_but_camera(const trt_ubo& a, const trt_ubo& b) {
            std::memcmp(reinterpret_cast<const char*>(&a) + cam + sizeof(trt_vec4),
                        reinterpret_cast<const char*>(&b) + cam + sizeof(trt_vec4),
                        sizeof(trt_ubo) - cam - sizeof(trt_vec4)) == 0;
+}
+
+// trt_check_rays / trt_check_segs: TRT_OK, or TRT_ERR_INVALID with the first record that fails.
+template <class R, class Valid>
+int first_invalid(const R* recs, uint32_t n, uint32_t* first_bad, Valid valid) {
+    if (first_bad) *first_bad = 0;
+    if (n && !recs) return TRT_ERR_INVALID;
+    for (uint32_t i = 0; i < n; ++i) {
+        if (valid(recs[i])) continue;
+        if (first_bad) *first_bad = i;
+        return TRT_ERR_INVALID;
+    }
+    return TRT_OK;
+}
+
+// A new context's knobs; the per-call ones, which tests change between calls, are read per call.
+void read_env_knobs(trt_ctx* c) {
+    if (const char* e = std::getenv("TRT_BVH_WAVES4")) c->bvh_waves4 = std::atoi(e) != 0 ? 1 : 0;
+    if (const char* e = std::getenv("TRT_SPP_LANES")) c->spp_lanes = std::atoi(e) != 0;
+    if (const char* e = std::getenv("TRT_DEFER_PPW")) { // pass-A pixels per wave: 64, 32, 16 or 8
+        const int ppw = std::atoi(e);
+        c->defer_sub = ppw == 8 ? 8u : ppw == 16 ? 4u : ppw == 32 ? 2u : ppw == 64 ? 1u : 0u;
+    }
+    if (const char* e = std::getenv("GPU_MAX_HW_QUEUES")) c->hw_queues = (uint32_t)std::max(1, std::atoi(e));
+    if (const char* e = std::getenv("TRT_DEFER_INTER")) c->defer_inter = (uint32_t)std::min(2, std::max(0, std::atoi(e)));
+    if (const char* e = std::getenv("TRT_DEFER_GROUP"))
+        c->defer_group = (uint32_t)std::min((int)trt::kMaxLaunchFrames, std::max(1, std::atoi(e)));
+    if (const char* e = std::getenv("TRT_DEFER_IN_FLIGHT")) {
+        c->defer_in_flight = (uint32_t)std::min((int)TRT_BUILD_MAX_IN_FLIGHT, std::max(1, std::atoi(e)));
+        c->defer_in_flight_set = true;
+    }
+    if (const char* e = std::getenv("TRT_XCD_ROT")) c->xcd_rot = (uint32_t)std::min(8, std::max(0, std::atoi(e)));
+    if (const char* e = std::getenv("TRT_XCD_SKEW")) c->xcd_skew = (uint32_t)std::min(7, std::max(0, std::atoi(e)));
+    if (const char* e = std::getenv("TRT_XCD_INTER")) c->xcd_inter = (uint32_t)std::min(2, std::max(0, std::atoi(e)));
+    if (const char* e = std::getenv("TRT_FRAME_GROUP")) c->frame_group = std::min(2, std::max(1, std::atoi(e)));
+    if (const char* e = std::getenv("TRT_SKY_TABLE")) c->sky_on = std::atoi(e) != 0;
+    if (const char* e = std::getenv("TRT_SKY_SPANS")) c->span_on = std::atoi(e) != 0;
+    if (const char* e = std::getenv("TRT_SKY_SPAN_FRAMES")) c->span_frames = (uint32_t)std::min(64, std::max(0, std::atoi(e)));
+    if (const char* e = std::getenv("TRT_SHADOW_MASK")) c->smask_on = std::atoi(e) != 0;
+    if (const char* e = std::getenv("TRT_FLOOR_CLASS")) c->floor_on = std::atoi(e) != 0;
+    if (const char* e = std::getenv("TRT_FLOOR_LIT")) c->floor_lit_on = std::atoi(e) != 0;
+    if (const char* e = std::getenv("TRT_SHADOW_MASK_CELL")) { // floor cell edge; the build clamps it
+        const float v = (float)std::atof(e);
+        if (v > 0.0f) c->smask_cell = v;
+    }
 }
 
 } // namespace
@@ -254,10 +220,7 @@ int trt_view_rays(const trt_params* p, const trt_view* v, trt_ray* out) {
             std::memset(&r, 0, sizeof(r));
             float w[3];
             view_pixel_dir(p, V, dz, x, y, w);
-            r.dir.x = w[0];
-            r.dir.y = w[1];
-            r.dir.z = w[2];
-            r.dir.w = 1.0f;
+            r.dir = {w[0], w[1], w[2], 1.0f};
         }
     }
     return TRT_OK;
@@ -273,31 +236,15 @@ int trt_pixel_ray(const trt_params* p, const trt_view* v, const float cam[3], ui
 }
 
 int trt_check_rays(const trt_qray* rays, uint32_t n, uint32_t* first_bad) {
-    if (first_bad) *first_bad = 0;
-    if (n == 0) return TRT_OK;
-    if (!rays) return TRT_ERR_INVALID;
-    for (uint32_t i = 0; i < n; ++i) {
-        const trt_qray& r = rays[i];
-        if (!trt::qray_valid(r.org[0], r.org[1], r.org[2], r.dir[0], r.dir[1], r.dir[2])) {
-            if (first_bad) *first_bad = i;
-            return TRT_ERR_INVALID;
-        }
-    }
-    return TRT_OK;
+    return first_invalid(rays, n, first_bad, [](const trt_qray& r) {
+        return trt::qray_valid(r.org[0], r.org[1], r.org[2], r.dir[0], r.dir[1], r.dir[2]);
+    });
 }
 
 int trt_check_segs(const trt_qseg* segs, uint32_t n, uint32_t* first_bad) {
-    if (first_bad) *first_bad = 0;
-    if (n == 0) return TRT_OK;
-    if (!segs) return TRT_ERR_INVALID;
-    for (uint32_t i = 0; i < n; ++i) {
-        const trt_qseg& s = segs[i];
-        if (!trt::qseg_valid(s.org[0], s.org[1], s.org[2], s.dir[0], s.dir[1], s.dir[2], s.tmax)) {
-            if (first_bad) *first_bad = i;
-            return TRT_ERR_INVALID;
-        }
-    }
-    return TRT_OK;
+    return first_invalid(segs, n, first_bad, [](const trt_qseg& s) {
+        return trt::qseg_valid(s.org[0], s.org[1], s.org[2], s.dir[0], s.dir[1], s.dir[2], s.tmax);
+    });
 }
 
 void trt_params_default(trt_params* p) {
@@ -345,34 +292,7 @@ int trt_create(trt_ctx** out, int hip_device) {
         trt_destroy(c);
         return TRT_ERR_HIP;
     }
-    if (const char* e = std::getenv("TRT_BVH_WAVES4")) c->bvh_waves4 = std::atoi(e) != 0 ? 1 : 0;
-    if (const char* e = std::getenv("TRT_SPP_LANES")) c->spp_lanes = std::atoi(e) != 0;
-    if (const char* e = std::getenv("TRT_DEFER_PPW")) { // pass-A pixels per wave: 64, 32, 16 or 8
-        const int ppw = std::atoi(e);
-        c->defer_sub = ppw == 8 ? 8u : ppw == 16 ? 4u : ppw == 32 ? 2u : ppw == 64 ? 1u : 0u;
-    }
-    if (const char* e = std::getenv("GPU_MAX_HW_QUEUES")) c->hw_queues = (uint32_t)std::max(1, std::atoi(e));
-    if (const char* e = std::getenv("TRT_DEFER_INTER")) c->defer_inter = (uint32_t)std::min(2, std::max(0, std::atoi(e)));
-    if (const char* e = std::getenv("TRT_DEFER_GROUP"))
-        c->defer_group = (uint32_t)std::min((int)trt::kMaxLaunchFrames, std::max(1, std::atoi(e)));
-    if (const char* e = std::getenv("TRT_DEFER_IN_FLIGHT")) {
-        c->defer_in_flight = (uint32_t)std::min((int)TRT_BUILD_MAX_IN_FLIGHT, std::max(1, std::atoi(e)));
-        c->defer_in_flight_set = true;
-    }
-    if (const char* e = std::getenv("TRT_XCD_ROT")) c->xcd_rot = (uint32_t)std::min(8, std::max(0, std::atoi(e)));
-    if (const char* e = std::getenv("TRT_XCD_SKEW")) c->xcd_skew = (uint32_t)std::min(7, std::max(0, std::atoi(e)));
-    if (const char* e = std::getenv("TRT_XCD_INTER")) c->xcd_inter = (uint32_t)std::min(2, std::max(0, std::atoi(e)));
-    if (const char* e = std::getenv("TRT_FRAME_GROUP")) c->frame_group = std::min(2, std::max(1, std::atoi(e)));
-    if (const char* e = std::getenv("TRT_SKY_TABLE")) c->sky_on = std::atoi(e) != 0;
-    if (const char* e = std::getenv("TRT_SKY_SPANS")) c->span_on = std::atoi(e) != 0;
-    if (const char* e = std::getenv("TRT_SKY_SPAN_FRAMES")) c->span_frames = (uint32_t)std::min(64, std::max(0, std::atoi(e)));
-    if (const char* e = std::getenv("TRT_SHADOW_MASK")) c->smask_on = std::atoi(e) != 0;
-    if (const char* e = std::getenv("TRT_FLOOR_CLASS")) c->floor_on = std::atoi(e) != 0;
-    if (const char* e = std::getenv("TRT_FLOOR_LIT")) c->floor_lit_on = std::atoi(e) != 0;
-    if (const char* e = std::getenv("TRT_SHADOW_MASK_CELL")) { // floor cell edge; the build clamps it
-        const float v = (float)std::atof(e);
-        if (v > 0.0f) c->smask_cell = v;
-    }
+    read_env_knobs(c);
     *out = c;
     return TRT_OK;
 }
@@ -386,29 +306,14 @@ int trt_destroy(trt_ctx* c) {
     // buffer below may be in use until the device drains
     (void)hipDeviceSynchronize();
     free_scene(c);
-    (void)hipFree(c->d_envp);
-    (void)hipFree(c->d_sky);
-    (void)hipFree(c->d_smask);
-    (void)hipFree(c->d_out8);
-    (void)hipFree(c->d_out32);
-    (void)hipFree(c->d_rays);
-    (void)hipFree(c->d_qrays);
-    (void)hipFree(c->d_qhits);
-    (void)hipFree(c->d_counters);
+    for (void* p : {(void*)c->d_envp, (void*)c->d_sky, (void*)c->d_smask, c->d_out8, c->d_out32, c->d_rays, c->d_qrays,
+                    c->d_qhits, (void*)c->d_counters})
+        (void)hipFree(p);
     for (hipEvent_t e : c->fev) (void)hipEventDestroy(e);
     for (auto& b : c->split) {
-        (void)hipFree(b.q[0]);
-        (void)hipFree(b.q[1]);
-        (void)hipFree(b.qlink[0]);
-        (void)hipFree(b.qlink[1]);
-        (void)hipFree(b.acc);
-        (void)hipFree(b.spilled);
-        (void)hipFree(b.ctr);
-        (void)hipFree(b.ev);
-        (void)hipFree(b.shq);
-        (void)hipFree(b.px_ev);
-        (void)hipFree(b.fb);
-        (void)hipFree(b.dctr);
+        for (void* p : {(void*)b.q[0], (void*)b.q[1], (void*)b.qlink[0], (void*)b.qlink[1], (void*)b.acc, (void*)b.spilled,
+                        (void*)b.ctr, (void*)b.ev, (void*)b.shq, (void*)b.px_ev, (void*)b.fb, (void*)b.dctr})
+            (void)hipFree(p);
         if (b.done) (void)hipEventDestroy(b.done);
     }
     for (hipStream_t s : c->aux) {
@@ -416,9 +321,8 @@ int trt_destroy(trt_ctx* c) {
         (void)hipStreamDestroy(s);
     }
     for (hipEvent_t e : c->aux_ev) (void)hipEventDestroy(e);
-    if (c->fork_ev) (void)hipEventDestroy(c->fork_ev);
-    if (c->ev0) (void)hipEventDestroy(c->ev0);
-    if (c->ev1) (void)hipEventDestroy(c->ev1);
+    for (hipEvent_t e : {c->fork_ev, c->ev0, c->ev1})
+        if (e) (void)hipEventDestroy(e);
     if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
     delete c;
     return TRT_OK;
@@ -493,210 +397,9 @@ int trt_update_ubo(trt_ctx* c, const trt_ubo* ubo) {
     return TRT_OK;
 }
 
-int trt_upload_scene(trt_ctx* c, const trt_ubo* ubo, const trt_triangle* tris, uint32_t ntri,
-                     const trt_model* models, uint32_t nmodel, const uint8_t* env,
-                     uint32_t env_w, uint32_t env_h) {
-    if (!c) return TRT_ERR_INVALID;
-    if (!ubo) return fail(c, TRT_ERR_INVALID, "trt_upload_scene: null ubo");
-    if (ntri && !tris) return fail(c, TRT_ERR_INVALID, "trt_upload_scene: null triangles");
-    if (nmodel && !models) return fail(c, TRT_ERR_INVALID, "trt_upload_scene: null models");
-    if (env && (env_w == 0 || env_h == 0))
-        return fail(c, TRT_ERR_INVALID, "trt_upload_scene: zero-size envmap");
-    for (uint32_t i = 0; i < nmodel; ++i) {
-        const int64_t s = models[i].params0.x, n = models[i].params0.y;
-        if (s < 0 || n < 0 || s + n > (int64_t)ntri)
-            return fail(c, TRT_ERR_INVALID,
-                        "trt_upload_scene: model " + std::to_string(i) +
-                            " triangle range outside the triangle buffer");
-    }
-    HIP_TRY(c, hipSetDevice(c->device));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    free_scene(c);
-
-    // Repack binding 6 (Model) and binding 5 (Triangle) for the wave-uniform walks.
-    std::vector<BatchRec> batches(nmodel);
-    for (uint32_t i = 0; i < nmodel; ++i) {
-        const trt_model& m = models[i];
-        BatchRec& b = batches[i];
-        b.bmin[0] = m.bboxMin.x;
-        b.bmin[1] = m.bboxMin.y;
-        b.bmin[2] = m.bboxMin.z;
-        b.bmax[0] = m.bboxMax.x;
-        b.bmax[1] = m.bboxMax.y;
-        b.bmax[2] = m.bboxMax.z;
-        b.start = m.params0.x;
-        b.count_ni = (m.params0.y & 0x7fffffff) | (m.params0.z != 0 ? (int32_t)0x80000000 : 0);
-    }
-    // Implicit 8-ary range hierarchy: node k of level L is the exact union of the boxes of
-    // batches [k*8^L, (k+1)*8^L).  A NaN coordinate anywhere below makes the node infinite
-    // (always entered), so culling stays conservative for degenerate input.
-    std::vector<float4> nodes;
-    uint32_t node_off[11] = {0};
-    uint32_t top = 0;
-    while (top < 10 && (1ull << (3 * top)) < (unsigned long long)nmodel) ++top;
-    {
-        std::vector<float4> prev_lo(nmodel), prev_hi(nmodel);
-        for (uint32_t i = 0; i < nmodel; ++i) {
-            const BatchRec& b = batches[i];
-            prev_lo[i] = make_float4(b.bmin[0], b.bmin[1], b.bmin[2], 0.0f);
-            prev_hi[i] = make_float4(b.bmax[0], b.bmax[1], b.bmax[2], 0.0f);
-        }
-        const float inf = std::numeric_limits<float>::infinity();
-        for (uint32_t L = 1; L <= top; ++L) {
-            const size_t n = (prev_lo.size() + 7) / 8;
-            node_off[L] = (uint32_t)(nodes.size() / 2);
-            std::vector<float4> lo(n), hi(n);
-            for (size_t k = 0; k < n; ++k) {
-                float4 a = make_float4(inf, inf, inf, 0.0f), z = make_float4(-inf, -inf, -inf, 0.0f);
-                bool bad = false;
-                for (size_t j = 8 * k; j < std::min(prev_lo.size(), 8 * k + 8); ++j) {
-                    const float4 &pl = prev_lo[j], &ph = prev_hi[j];
-                    bad |= std::isnan(pl.x) || std::isnan(pl.y) || std::isnan(pl.z) || std::isnan(ph.x) ||
-                           std::isnan(ph.y) || std::isnan(ph.z);
-                    // the reference's slab test takes min / max of the two planes per axis, so a
-                    // batch box with bboxMin > bboxMax on an axis (a caller's, or the builder's
-                    // untouched FLT_MAX / -FLT_MAX sentinels when every vertex is NaN there) is the
-                    // slab between the planes, not an empty one: the union orders the planes first
-                    const float4 l = make_float4(std::min(pl.x, ph.x), std::min(pl.y, ph.y), std::min(pl.z, ph.z), 0.0f);
-                    const float4 h = make_float4(std::max(pl.x, ph.x), std::max(pl.y, ph.y), std::max(pl.z, ph.z), 0.0f);
-                    a.x = std::min(a.x, l.x); a.y = std::min(a.y, l.y); a.z = std::min(a.z, l.z);
-                    z.x = std::max(z.x, h.x); z.y = std::max(z.y, h.y); z.z = std::max(z.z, h.z);
-                }
-                if (bad) {
-                    a = make_float4(-inf, -inf, -inf, 0.0f);
-                    z = make_float4(inf, inf, inf, 0.0f);
-                }
-                lo[k] = a;
-                hi[k] = z;
-                nodes.push_back(a);
-                nodes.push_back(z);
-            }
-            prev_lo.swap(lo);
-            prev_hi.swap(hi);
-        }
-    }
-    std::vector<TriGeo> geo(ntri);
-    std::vector<TriShade> shade(ntri);
-    std::vector<Mat> mats;
-    std::map<std::string, uint32_t> mat_index;
-    for (uint32_t j = 0; j < ntri; ++j) {
-        const trt_triangle& t = tris[j];
-        TriGeo& g = geo[j];
-        g.v0[0] = t.v0.x;
-        g.v0[1] = t.v0.y;
-        g.v0[2] = t.v0.z;
-        // edge1 = v1 - v0, edge2 = v2 - v0 (shader.comp:230-231): same float subtraction
-        g.e1[0] = t.v1.x - t.v0.x;
-        g.e1[1] = t.v1.y - t.v0.y;
-        g.e1[2] = t.v1.z - t.v0.z;
-        g.e2[0] = t.v2.x - t.v0.x;
-        g.e2[1] = t.v2.y - t.v0.y;
-        g.e2[2] = t.v2.z - t.v0.z;
-        g.pad[0] = g.pad[1] = g.pad[2] = 0.0f;
-        TriShade& s = shade[j];
-        s.n0[0] = t.v0_norm.x;
-        s.n0[1] = t.v0_norm.y;
-        s.n0[2] = t.v0_norm.z;
-        s.n1[0] = t.v1_norm.x;
-        s.n1[1] = t.v1_norm.y;
-        s.n1[2] = t.v1_norm.z;
-        s.n2[0] = t.v2_norm.x;
-        s.n2[1] = t.v2_norm.y;
-        s.n2[2] = t.v2_norm.z;
-        std::string key(reinterpret_cast<const char*>(&t.material), sizeof(trt_material));
-        auto it = mat_index.find(key);
-        if (it == mat_index.end()) {
-            it = mat_index.emplace(key, (uint32_t)mats.size()).first;
-            mats.push_back(to_mat(t.material));
-        }
-        s.material = it->second;
-        s.pad[0] = s.pad[1] = 0;
-    }
-    if (mats.empty()) mats.push_back(Mat{});
-
-    auto upload = [&](void** dst, const void* src, size_t bytes, const char* what) -> int {
-        if (bytes == 0) bytes = 16; // never bind a null buffer
-        hipError_t e = hipMalloc(dst, bytes);
-        if (e != hipSuccess) return hip_fail(c, e, what);
-        if (src) {
-            e = hipMemcpy(*dst, src, bytes, hipMemcpyHostToDevice);
-            if (e != hipSuccess) return hip_fail(c, e, what);
-        }
-        return TRT_OK;
-    };
-    int rc;
-    if ((rc = upload((void**)&c->d_batches, nmodel ? batches.data() : nullptr,
-                     sizeof(BatchRec) * nmodel, "upload batches")) != TRT_OK ||
-        (rc = upload((void**)&c->d_geo, ntri ? geo.data() : nullptr, sizeof(TriGeo) * ntri,
-                     "upload triangle geometry")) != TRT_OK ||
-        (rc = upload((void**)&c->d_shade, ntri ? shade.data() : nullptr, sizeof(TriShade) * ntri,
-                     "upload triangle shading")) != TRT_OK ||
-        (rc = upload((void**)&c->d_mats, mats.data(), sizeof(Mat) * mats.size(),
-                     "upload materials")) != TRT_OK ||
-        (rc = upload((void**)&c->d_nodes, nodes.empty() ? nullptr : nodes.data(), sizeof(float4) * nodes.size(),
-                     "upload batch hierarchy")) != TRT_OK) {
-        free_scene(c);
-        return rc;
-    }
-    std::vector<trt::BvhNode> bvh;
-    std::vector<TriGeo> bvh_tris;
-    size_t bvh4_n = 0;
-    if (nmodel && trt::build_bvh(tris, ntri, models, nmodel, bvh, bvh_tris)) {
-        std::vector<trt::Bvh4Node> bvh4;
-        // the 4-wide walk only when its worst-case stack fits (else the BVH2 walk: <= depth)
-        if (trt::collapse_bvh4(bvh, bvh4) > (uint32_t)trt::kBvhStack) bvh4.clear();
-        bvh4_n = bvh4.size();
-        std::vector<trt::Bvh4QNode> bvh4q;
-        const bool quant = !bvh4.empty() && trt::quantize_bvh4(bvh4, bvh4q);
-        if (quant && (rc = upload((void**)&c->d_bvh4q, bvh4q.data(), sizeof(trt::Bvh4QNode) * bvh4q.size(),
-                                  "upload quantized bvh4")) != TRT_OK) {
-            free_scene(c);
-            return rc;
-        }
-        if ((rc = upload((void**)&c->d_bvh, bvh.data(), sizeof(trt::BvhNode) * bvh.size(), "upload bvh")) != TRT_OK ||
-            (!bvh4.empty() && (rc = upload((void**)&c->d_bvh4, bvh4.data(), sizeof(trt::Bvh4Node) * bvh4.size(),
-                                            "upload bvh4")) != TRT_OK) ||
-            (rc = upload((void**)&c->d_bvh_tris, bvh_tris.data(), sizeof(TriGeo) * bvh_tris.size(),
-                         "upload bvh triangles")) != TRT_OK) {
-            free_scene(c);
-            return rc;
-        }
-    }
-    if (env) {
-        if ((rc = upload((void**)&c->d_env, env, (size_t)env_w * env_h * 4, "upload envmap")) != TRT_OK) {
-            free_scene(c);
-            return rc;
-        }
-        c->env_w = env_w;
-        c->env_h = env_h;
-    }
-    size_t* sb = c->scene_bytes;
-    std::memset(sb, 0, sizeof(c->scene_bytes));
-    sb[trt::kSceneBatches] = std::max<size_t>(sizeof(BatchRec) * nmodel, 16);
-    sb[trt::kSceneNodes] = std::max<size_t>(sizeof(float4) * nodes.size(), 16);
-    sb[trt::kSceneGeo] = std::max<size_t>(sizeof(TriGeo) * ntri, 16);
-    sb[trt::kSceneShade] = std::max<size_t>(sizeof(TriShade) * ntri, 16);
-    sb[trt::kSceneMats] = sizeof(Mat) * mats.size();
-    if (c->d_bvh) {
-        sb[trt::kSceneBvh] = sizeof(trt::BvhNode) * bvh.size();
-        sb[trt::kSceneBvhTris] = sizeof(TriGeo) * bvh_tris.size();
-    }
-    if (c->d_bvh4) sb[trt::kSceneBvh4] = sizeof(trt::Bvh4Node) * bvh4_n;
-    if (c->d_bvh4q) sb[trt::kSceneBvh4Q] = sizeof(trt::Bvh4QNode) * bvh4_n;
-    if (c->d_env) sb[trt::kSceneEnv] = (size_t)env_w * env_h * 4;
-    c->nbatch = nmodel;
-    c->top = top;
-    std::memcpy(c->node_off, node_off, sizeof(node_off));
-    c->ntri = ntri;
-    c->nmat = (uint32_t)mats.size();
-    c->ubo = *ubo;
-    c->have_scene = true;
-    return TRT_OK;
-}
-
 } // extern "C"
 
-namespace {
+namespace trt {
 
 // Builds the envmap pair rows (KArgs::envp) on `stream` when d_env changed since the last
 // build.  Without them (TRT_ENV_PAIRROWS=0 in the environment) env_fetch reads d_env directly.
@@ -720,6 +423,109 @@ int ensure_envp(trt_ctx* c, const trt_params* p, hipStream_t stream) {
     c->envp_ok = true;
     return TRT_OK;
 }
+
+// attach_floor_class's floor_lit (kFloorLit beside the class bit, sky_trace_kernel_floor_lit): the
+// floor's three channels are one value and every light shines on its upper side, which floor_frame LIT relies on.
+// Not under TRT_FLOOR_LIT=0: the launch then runs sky_trace_kernel_floor as before.
+uint32_t floor_lit(uint32_t flags, const float (*light)[3]) {
+    if (flags & TRT_FLAG_CHECKER) return 0u;
+    for (int i = 0; i < 3; ++i)
+        if (!(light[i][1] + 4.0f > trt::kFloorLitPad)) return 0u; // NaN too
+    return 1u;
+}
+
+int check_params(trt_ctx* c, const trt_params* p) {
+    if (!p) return fail(c, TRT_ERR_INVALID, "trt_render: null params");
+    if (!c->have_scene) return fail(c, TRT_ERR_NOSCENE, "trt_render: no scene uploaded");
+    if (p->width == 0 || p->height == 0 || p->width > 65536 || p->height > 65536)
+        return fail(c, TRT_ERR_INVALID, "trt_render: image size out of range");
+    if (p->max_depth < 1 || p->max_depth > TRT_MAX_DEPTH_LIMIT)
+        return fail(c, TRT_ERR_INVALID, "trt_render: max_depth must be 1..20");
+    if (p->spp > 4096) return fail(c, TRT_ERR_INVALID, "trt_render: spp must be <= 4096");
+    if (p->band_rows && p->band_count > 1 && p->band_index >= p->band_count)
+        return fail(c, TRT_ERR_INVALID, "trt_render: band_index >= band_count");
+    if ((p->flags & TRT_FLAG_BAND_IN_PLACE) && !(p->flags & TRT_FLAG_DEVICE_PTRS))
+        return fail(c, TRT_ERR_INVALID, "trt_render: TRT_FLAG_BAND_IN_PLACE needs TRT_FLAG_DEVICE_PTRS");
+    if ((p->flags & TRT_FLAG_ENVMAP) && !c->d_env)
+        return fail(c, TRT_ERR_INVALID, "trt_render: TRT_FLAG_ENVMAP without an uploaded envmap");
+    return TRT_OK;
+}
+
+// Everything of KArgs that does not depend on the UBO or the output pointers.
+void fill_args(trt_ctx* c, const trt_params* p, KArgs& A) {
+    std::memset(&A, 0, sizeof(A));
+    A.width = p->width;
+    A.height = p->height;
+    A.rows = trt_output_rows(p);
+    A.band_rows = p->band_rows;
+    A.band_count = p->band_count;
+    A.band_index = p->band_index;
+    A.max_depth = p->max_depth;
+    A.spp = p->spp ? p->spp : 1;
+    // spp a power of two in [2, 64] and no replayed rays: one lane per sample (trace_samples;
+    // TRT_SPP_LANES=0 keeps the per-pixel sample loop)
+    A.spp_lanes = (A.spp >= 2u && A.spp <= 64u && (A.spp & (A.spp - 1u)) == 0u && !p->rays_in && c->spp_lanes) ? 1u : 0u;
+    A.seed = p->seed;
+    A.flags = p->flags;
+    A.dz = view_dz(p);
+    A.nbatch = c->nbatch;
+    fill_ubo_args(A, c->ubo);
+    A.nframes = 1;
+    fill_frame(A.fr[0], c->ubo, nullptr, (p->flags & TRT_FLAG_BAND_IN_PLACE) != 0);
+    // the context's view (trt_set_view); replayed rays are the caller's directions and win
+    A.view_on = (c->view_on && !p->rays_in) ? 1u : 0u;
+    if (A.view_on) fill_view(A, 0, c->view);
+    A.batches = c->d_batches;
+    A.geo = c->d_geo;
+    A.shade = c->d_shade;
+    A.mats = c->d_mats;
+    A.env = c->d_env;
+    A.envp = c->envp_ok ? c->d_envp : nullptr;
+    A.env_w = c->env_w;
+    A.env_h = c->env_h;
+    A.counters = c->d_counters;
+    A.nodes = c->d_nodes;
+    A.bvh = c->d_bvh;
+    A.bvh4 = c->d_bvh4;
+    A.bvh4q = c->d_bvh4q;
+    A.diag = reinterpret_cast<float4*>(c->diag);
+    A.bvh_tris = c->d_bvh_tris;
+    A.top = c->top;
+    std::memcpy(A.node_off, c->node_off, sizeof(A.node_off));
+    A.ntx = (A.width + 7u) / 8u;
+    A.ntiles = A.ntx * ((A.rows + 7u) / 8u);
+    // The BVH walk at 4 waves per SIMD (GEOM 3: <= 128 VGPRs, 16-entry LDS stack, quantized
+    // nodes) hides more of the node-fetch latency than the 3-wave build.  Round 1 measured it
+    // for large scenes only (C4 -13 %, C3 / shipped frame +1 %, profiles/r01_ab_occupancy.log);
+    // since the traversal stack's index left scratch memory (round 3) it is ahead or equal
+    // everywhere: C4 2.90 vs 3.38 ms, C3 -9 %, shipped frame and README scene within 1 %
+    // (profiles/r03_ab_waves4_after_stack_fix.log), so it is the default for every BVH scene.
+    // GEOM 3 kernels walk only the quantized nodes (trt_kernel.hip g3_quant_only): a scene whose
+    // nodes did not quantize (or whose 4-wide stack would not fit) takes the GEOM 2 kernels.
+    A.bvh_waves4 = c->d_bvh4q ? (c->bvh_waves4 >= 0 ? (uint32_t)c->bvh_waves4 : 1u) : 0u;
+    A.xcd_rot = c->xcd_rot;
+    A.xcd_skew = c->xcd_skew;
+    A.xcd_inter = c->xcd_inter;
+    {   // xcd_inter 2: a multiplier near 0.618 of the dealt chunk count, coprime to it (a
+        // golden-ratio step spreads each XCD's chunks evenly over the image)
+        const uint32_t tyn = (A.rows + 7u) / 8u;
+        const uint32_t nfull = ((A.ntx / 2u) * (tyn / 2u) / 8u) * 8u;
+        uint32_t m = nfull ? (uint32_t)(0.6180339887 * nfull) | 1u : 1u;
+        auto gcd = [](uint32_t a, uint32_t b) { while (b) { const uint32_t t = a % b; a = b; b = t; } return a; };
+        while (nfull && gcd(m, nfull) != 1u) m += 2u;
+        A.xcd_mult = nfull ? m % nfull : 1u;
+        if (A.xcd_mult == 0u || nfull >= 65536u) A.xcd_mult = 1u; // the kernel's k * mult stays in 32 bits
+    }
+    // Frame groups (trace_kernel): triangle-free frames (C2) 14.8 -> 13.85 us per frame at
+    // 20-frame launches with pairs; mesh frames lose (C4 +2.5 %, C3 +10 %: their tiles' costs
+    // vary more from frame to frame and a pair doubles the longest wave),
+    // profiles/r03_ab_frame_pair.log
+    A.frame_group = c->frame_group > 0 ? (uint32_t)c->frame_group : (c->nbatch == 0 ? 2u : 1u);
+}
+
+} // namespace trt
+
+namespace {
 
 // The sky table of a frame's arguments (KArgs::sky), or null when the frame does not use one.
 // The table serves triangle-free plain frames at spp 1 that neither replay rays (rays_in) nor
@@ -879,17 +685,6 @@ int attach_smask(trt_ctx* c, KArgs& A, hipStream_t stream) {
 // TRT_FLOOR_CLASS=0, keeps its span words and runs the kernel it ran before.  So does a launch of
 // one frame: frames launched one by one were 1.5-2.2 % slower with the class than without
 // (profiles/floor_class_ab_summary.txt), so they neither compute the intervals nor change kernel.
-//
-// floor_lit (kFloorLit beside the class bit, sky_trace_kernel_floor_lit): the floor's three
-// channels are one value and every light shines on its upper side, which floor_frame LIT relies on.
-// Not under TRT_FLOOR_LIT=0: the launch then runs sky_trace_kernel_floor as before.
-uint32_t floor_lit(uint32_t flags, const float (*light)[3]) {
-    if (flags & TRT_FLAG_CHECKER) return 0u;
-    for (int i = 0; i < 3; ++i)
-        if (!(light[i][1] + 4.0f > trt::kFloorLitPad)) return 0u; // NaN too
-    return 1u;
-}
-
 void attach_floor_class(const trt_ctx* c, KArgs& A) {
     A.floor_class = 0;
     if (!c->floor_on || A.nframes < 2u || !A.span_tables || !A.smask || A.ntx > trt::kFloorPackMaxNtx) return;
@@ -900,94 +695,19 @@ void attach_floor_class(const trt_ctx* c, KArgs& A) {
     if (c->floor_lit_on && floor_lit(A.flags, A.light)) A.floor_class |= trt::kFloorLit;
 }
 
-int check_params(trt_ctx* c, const trt_params* p) {
-    if (!p) return fail(c, TRT_ERR_INVALID, "trt_render: null params");
-    if (!c->have_scene) return fail(c, TRT_ERR_NOSCENE, "trt_render: no scene uploaded");
-    if (p->width == 0 || p->height == 0 || p->width > 65536 || p->height > 65536)
-        return fail(c, TRT_ERR_INVALID, "trt_render: image size out of range");
-    if (p->max_depth < 1 || p->max_depth > TRT_MAX_DEPTH_LIMIT)
-        return fail(c, TRT_ERR_INVALID, "trt_render: max_depth must be 1..20");
-    if (p->spp > 4096) return fail(c, TRT_ERR_INVALID, "trt_render: spp must be <= 4096");
-    if (p->band_rows && p->band_count > 1 && p->band_index >= p->band_count)
-        return fail(c, TRT_ERR_INVALID, "trt_render: band_index >= band_count");
-    if ((p->flags & TRT_FLAG_BAND_IN_PLACE) && !(p->flags & TRT_FLAG_DEVICE_PTRS))
-        return fail(c, TRT_ERR_INVALID, "trt_render: TRT_FLAG_BAND_IN_PLACE needs TRT_FLAG_DEVICE_PTRS");
-    if ((p->flags & TRT_FLAG_ENVMAP) && !c->d_env)
-        return fail(c, TRT_ERR_INVALID, "trt_render: TRT_FLAG_ENVMAP without an uploaded envmap");
+// Launch preparation, once the frames, the UBO, A.sky and A.view_on are set.  The order is a
+// correctness condition: the floor class needs the masks and repacks A.span in place from
+// c->sph_span, which fill_spans left behind; the bases of an oriented launch (views[f], null: the
+// identity; views null: fill_args wrote the one basis) share their bytes with the span words, so
+// they come last (an oriented launch has no table, hence no span words).
+int prepare_launch(trt_ctx* c, KArgs& A, hipStream_t stream, const trt_view* const* views) {
+    fill_spans(c, A);
+    const int rc = attach_smask(c, A, stream);
+    if (rc != TRT_OK) return rc;
+    attach_floor_class(c, A);
+    if (A.view_on && views)
+        for (uint32_t f = 0; f < A.nframes; ++f) fill_view(A, f, views[f] ? *views[f] : kViewIdentity);
     return TRT_OK;
-}
-
-// Everything of KArgs that does not depend on the UBO or the output pointers.
-void fill_args(trt_ctx* c, const trt_params* p, KArgs& A) {
-    std::memset(&A, 0, sizeof(A));
-    A.width = p->width;
-    A.height = p->height;
-    A.rows = trt_output_rows(p);
-    A.band_rows = p->band_rows;
-    A.band_count = p->band_count;
-    A.band_index = p->band_index;
-    A.max_depth = p->max_depth;
-    A.spp = p->spp ? p->spp : 1;
-    // spp a power of two in [2, 64] and no replayed rays: one lane per sample (trace_samples;
-    // TRT_SPP_LANES=0 keeps the per-pixel sample loop)
-    A.spp_lanes = (A.spp >= 2u && A.spp <= 64u && (A.spp & (A.spp - 1u)) == 0u && !p->rays_in && c->spp_lanes) ? 1u : 0u;
-    A.seed = p->seed;
-    A.flags = p->flags;
-    // dir_z = -1.0 * (HEIGHT / (2.0 * tan(fov / 2.0))) in double, main.cpp:1503
-    A.dz = (float)(-1.0 * ((double)p->height / (2.0 * std::tan((double)p->fov / 2.0))));
-    A.nbatch = c->nbatch;
-    fill_ubo_args(A, c->ubo);
-    A.nframes = 1;
-    fill_frame(A.fr[0], c->ubo, nullptr, (p->flags & TRT_FLAG_BAND_IN_PLACE) != 0);
-    // the context's view (trt_set_view); replayed rays are the caller's directions and win
-    A.view_on = (c->view_on && !p->rays_in) ? 1u : 0u;
-    if (A.view_on) fill_view(A, 0, c->view);
-    A.batches = c->d_batches;
-    A.geo = c->d_geo;
-    A.shade = c->d_shade;
-    A.mats = c->d_mats;
-    A.env = c->d_env;
-    A.envp = c->envp_ok ? c->d_envp : nullptr;
-    A.env_w = c->env_w;
-    A.env_h = c->env_h;
-    A.counters = c->d_counters;
-    A.nodes = c->d_nodes;
-    A.bvh = c->d_bvh;
-    A.bvh4 = c->d_bvh4;
-    A.bvh4q = c->d_bvh4q;
-    A.diag = reinterpret_cast<float4*>(c->diag);
-    A.bvh_tris = c->d_bvh_tris;
-    A.top = c->top;
-    std::memcpy(A.node_off, c->node_off, sizeof(A.node_off));
-    A.ntx = (A.width + 7u) / 8u;
-    A.ntiles = A.ntx * ((A.rows + 7u) / 8u);
-    // The BVH walk at 4 waves per SIMD (GEOM 3: <= 128 VGPRs, 16-entry LDS stack, quantized
-    // nodes) hides more of the node-fetch latency than the 3-wave build.  Round 1 measured it
-    // for large scenes only (C4 -13 %, C3 / shipped frame +1 %, profiles/r01_ab_occupancy.log);
-    // since the traversal stack's index left scratch memory (round 3) it is ahead or equal
-    // everywhere: C4 2.90 vs 3.38 ms, C3 -9 %, shipped frame and README scene within 1 %
-    // (profiles/r03_ab_waves4_after_stack_fix.log), so it is the default for every BVH scene.
-    // GEOM 3 kernels walk only the quantized nodes (trt_kernel.hip g3_quant_only): a scene whose
-    // nodes did not quantize (or whose 4-wide stack would not fit) takes the GEOM 2 kernels.
-    A.bvh_waves4 = c->d_bvh4q ? (c->bvh_waves4 >= 0 ? (uint32_t)c->bvh_waves4 : 1u) : 0u;
-    A.xcd_rot = c->xcd_rot;
-    A.xcd_skew = c->xcd_skew;
-    A.xcd_inter = c->xcd_inter;
-    {   // xcd_inter 2: a multiplier near 0.618 of the dealt chunk count, coprime to it (a
-        // golden-ratio step spreads each XCD's chunks evenly over the image)
-        const uint32_t tyn = (A.rows + 7u) / 8u;
-        const uint32_t nfull = ((A.ntx / 2u) * (tyn / 2u) / 8u) * 8u;
-        uint32_t m = nfull ? (uint32_t)(0.6180339887 * nfull) | 1u : 1u;
-        auto gcd = [](uint32_t a, uint32_t b) { while (b) { const uint32_t t = a % b; a = b; b = t; } return a; };
-        while (nfull && gcd(m, nfull) != 1u) m += 2u;
-        A.xcd_mult = nfull ? m % nfull : 1u;
-        if (A.xcd_mult == 0u || nfull >= 65536u) A.xcd_mult = 1u; // the kernel's k * mult stays in 32 bits
-    }
-    // Frame groups (trace_kernel): triangle-free frames (C2) 14.8 -> 13.85 us per frame at
-    // 20-frame launches with pairs; mesh frames lose (C4 +2.5 %, C3 +10 %: their tiles' costs
-    // vary more from frame to frame and a pair doubles the longest wave),
-    // profiles/r03_ab_frame_pair.log
-    A.frame_group = c->frame_group > 0 ? (uint32_t)c->frame_group : (c->nbatch == 0 ? 2u : 1u);
 }
 
 // Does this frame run deferred shadows?  Auto: mesh scenes with max_depth >= 8, whose deep
@@ -1128,14 +848,8 @@ uint32_t fit_defer_slots(const trt_ctx* c, const trt_params* p, uint32_t want, u
 }
 
 void free_defer_bufs(trt_ctx::SplitBufs& b) {
-    void* ps[] = {b.ev, b.shq, b.px_ev, b.fb};
-    for (void* q : ps) (void)hipFree(q);
-    (void)hipFree(b.dctr);
-    b.ev = nullptr;
-    b.shq = nullptr;
-    b.px_ev = nullptr;
-    b.fb = nullptr;
-    b.dctr = nullptr;
+    for (void** q : {(void**)&b.ev, (void**)&b.shq, (void**)&b.px_ev, (void**)&b.fb, (void**)&b.dctr})
+        (void)hipFree(*q), *q = nullptr;
     b.ev_chunks = b.shq_cap = b.dnpx = 0;
     b.dframes = 0;
 }
@@ -1228,12 +942,9 @@ int prepare_split(trt_ctx* c, const trt_params* p, KArgs& A, uint32_t slot, hipS
         // the pixel in place)
         const size_t cap = std::min<size_t>(std::max<size_t>(4 * npx, 1u << 16), 1u << 28);
         auto drop = [&] {
-            for (auto*& q : b.q) (void)hipFree(q), q = nullptr;
-            for (auto*& q : b.qlink) (void)hipFree(q), q = nullptr;
-            (void)hipFree(b.acc);
-            (void)hipFree(b.spilled);
-            b.acc = nullptr;
-            b.spilled = nullptr;
+            for (void** q : {(void**)&b.q[0], (void**)&b.q[1], (void**)&b.qlink[0], (void**)&b.qlink[1], (void**)&b.acc,
+                             (void**)&b.spilled})
+                (void)hipFree(*q), *q = nullptr;
             b.npx = 0;
             b.cap = 0;
         };
@@ -1277,26 +988,14 @@ int fence_split(trt_ctx* c, const KArgs& A, uint32_t slot, hipStream_t stream) {
 
 // trt_stats from the device counters, in KArgs::counters order (kernel_ms is the caller's).
 void stats_from_counters(trt_stats* st, const unsigned long long* cnt) {
-    st->primary_rays = cnt[0];
-    st->secondary_rays = cnt[1];
-    st->shadow_rays = cnt[2];
-    st->misses = cnt[3];
-    st->tri_nearest = cnt[4];
-    st->sphere_tests = cnt[5];
-    st->batch_tests = cnt[6];
-    st->batch_hits = cnt[7];
-    st->tri_tests = cnt[8];
-    st->node_tests = cnt[9];
-    st->tri_past_a = cnt[10];
-    st->tri_past_u = cnt[11];
-    st->tri_past_v = cnt[12];
-    st->shadow_skipped = cnt[13];
-    st->skipped_sphere_tests = cnt[14];
-    st->skipped_box_tests = cnt[15];
-    st->skipped_tri_tests = cnt[16];
-    st->skipped_tri_past_a = cnt[17];
-    st->skipped_tri_past_u = cnt[18];
-    st->skipped_tri_past_v = cnt[19];
+    static uint64_t trt_stats::*const field[20] = {
+        &trt_stats::primary_rays, &trt_stats::secondary_rays, &trt_stats::shadow_rays, &trt_stats::misses,
+        &trt_stats::tri_nearest, &trt_stats::sphere_tests, &trt_stats::batch_tests, &trt_stats::batch_hits,
+        &trt_stats::tri_tests, &trt_stats::node_tests, &trt_stats::tri_past_a, &trt_stats::tri_past_u,
+        &trt_stats::tri_past_v, &trt_stats::shadow_skipped, &trt_stats::skipped_sphere_tests,
+        &trt_stats::skipped_box_tests, &trt_stats::skipped_tri_tests, &trt_stats::skipped_tri_past_a,
+        &trt_stats::skipped_tri_past_u, &trt_stats::skipped_tri_past_v};
+    for (int i = 0; i < 20; ++i) st->*field[i] = cnt[i];
 }
 
 // trt_render's split slot: one per distinct stream among the last TRT_BUILD_MAX_IN_FLIGHT
@@ -1308,6 +1007,144 @@ uint32_t render_slot(trt_ctx* c, hipStream_t s) {
     c->render_slot_next = (k + 1) % TRT_BUILD_MAX_IN_FLIGHT;
     c->render_slot_stream[k] = s;
     return k;
+}
+
+// Before the launch of trt_render, trt_trace_rays and trt_occluded; finish_call after it.
+int begin_call(trt_ctx* c, bool count, bool timing) {
+    if (count) HIP_TRY(c, hipMemsetAsync(c->d_counters, 0, 32 * sizeof(unsigned long long), c->stream));
+    if (timing) HIP_TRY(c, hipEventRecord(c->ev0, c->stream));
+    return TRT_OK;
+}
+
+// A host array staged through a grow-only buffer of the context: `in`, when given, is copied to
+// it; *dev is the array's device twin (finish_call copies outputs back).
+template <class T>
+int stage(trt_ctx* c, void** buf, size_t* cap, size_t bytes, const char* what, const void* in, T** dev) {
+    const int rc = ensure(c, buf, cap, bytes, what);
+    if (rc != TRT_OK) return rc;
+    if (in) HIP_TRY(c, hipMemcpyAsync(*buf, in, bytes, hipMemcpyHostToDevice, c->stream));
+    *dev = static_cast<T*>(*buf);
+    return TRT_OK;
+}
+struct StagedOut { void* host; const void* dev; size_t bytes; }; // host null: not asked for
+// The stream is synchronised when the caller reads anything on return.
+int finish_call(trt_ctx* c, bool dev, bool count, bool timing, trt_stats* st, std::initializer_list<StagedOut> outs) {
+    if (timing) HIP_TRY(c, hipEventRecord(c->ev1, c->stream));
+    if (!dev)
+        for (const StagedOut& o : outs)
+            if (o.host) HIP_TRY(c, hipMemcpyAsync(o.host, o.dev, o.bytes, hipMemcpyDeviceToHost, c->stream));
+    unsigned long long cnt[32] = {0};
+    if (count) HIP_TRY(c, hipMemcpyAsync(cnt, c->d_counters, sizeof(cnt), hipMemcpyDeviceToHost, c->stream));
+    if (!dev || count || timing) HIP_TRY(c, hipStreamSynchronize(c->stream));
+    if (st) {
+        stats_from_counters(st, cnt);
+        st->kernel_ms = 0.0;
+        if (timing) {
+            float ms = 0.0f;
+            HIP_TRY(c, hipEventElapsedTime(&ms, c->ev0, c->ev1));
+            st->kernel_ms = ms;
+        }
+    }
+    return TRT_OK;
+}
+
+// What a query reads of p, as frame params for fill_args: 64 x 1 pixels that reach no kernel.
+trt_params query_params(const trt_params* p, uint32_t max_depth, uint32_t flag_mask) {
+    trt_params q;
+    trt_params_default(&q);
+    q.width = 64;
+    q.height = 1;
+    q.max_depth = max_depth;
+    q.flags = p->flags & flag_mask;
+    return q;
+}
+
+// The shape of a frame loop: `want` in-flight slots and `per_launch` frames per launch.
+// Plain frames (no subtree split, no deferred shadows: the same decision prepare_split
+// makes) go out several per launch; the others one per launch (per-slot scratch).
+// Frames in flight (main.cpp:45, MAX_FRAMES_IN_FLIGHT): launch j runs on slot j % n.  Slot 0
+// is the context's stream, slots 1..n-1 are context-owned streams forked from it and joined
+// back into it, so to the caller all frames complete on its stream.  A
+// plain loop needs no second slot: one multi-frame launch keeps the GPU full from its first frame
+// to its last, so a 20-frame loop is one launch and drains once (C2 at 20 frames: 20.5 us per
+// frame against 25.0 with one launch per frame on 4 slots; at 1000 frames 15.6 vs 15.9,
+// profiles/r03_ab_frame_batch.log); with n slots set explicitly the frames are spread over
+// n launches.  Per-frame launch sequences (split / deferred-shadow frames) keep the slots
+// busy instead: auto 4, or defer_in_flight (16) for deferred-shadow frames (8 vs 16 in round
+// 4: the shipped frame 0.42 -> 0.35 ms, the README scene 0.24 -> 0.17 ms,
+// profiles/r04z_ab_deferred_in_flight.jsonl; round 2: the shipped frame 1.45 -> 0.56 ms at
+// 8, profiles/r02_ab_queues_deep.log).
+uint32_t loop_shape(const trt_ctx* c, const trt_params* p, uint32_t nframes, uint32_t& want) {
+    const bool defer = defer_frame(c, p);
+    const bool split = (defer || !defer_frame(c, p, true)) && split_window(c, p) != 0;
+    const bool plain = !defer && !split;
+    want = c->frames_in_flight ? c->frames_in_flight : plain ? 1u : defer ? c->defer_in_flight : 4u;
+    // auto: no more deferred slots than device memory holds (each slot owns its scratch)
+    // deferred frames (not split) go out in groups of frames per launch sequence (defer_shape)
+    uint32_t group = 1;
+    if (defer && !split) {
+        uint32_t slots = want;
+        defer_shape(c, group, slots);
+        group = std::min(group, trt::kMaxLaunchFrames);
+        want = slots;
+    }
+    if (!c->frames_in_flight && defer) want = fit_defer_slots(c, p, want, group);
+    const uint32_t cap = plain ? (c->frame_batch ? c->frame_batch : trt::kMaxLaunchFrames) : group;
+    return std::max(1u, std::min(cap, (nframes + want - 1) / want));
+}
+
+// launches: runs of consecutive frames sharing every UBO field but camPos; run j is frames
+// [first[j], first[j + 1]).  Views do not split launches; a launch with an oriented frame holds
+// at most kMaxViewFrames frames (one basis each in KArgs::view), so a run breaks where it would
+// outgrow that
+template <class ViewOf, class UboOf>
+std::vector<uint32_t> launch_runs(ViewOf view_of, UboOf ubo_of, uint32_t nframes, uint32_t per_launch) {
+    std::vector<uint32_t> first{0};
+    bool run_oriented = view_of(0) != nullptr;
+    for (uint32_t i = 1; i < nframes; ++i) {
+        const bool o = view_of(i) != nullptr;
+        const uint32_t len = i - first.back();
+        const bool cut = len >= per_launch || !same_but_camera(ubo_of(i), ubo_of(first.back())) ||
+                         ((run_oriented || o) && len >= trt::kMaxViewFrames);
+        if (cut) first.push_back(i);
+        run_oriented = o || (run_oriented && !cut);
+    }
+    first.push_back(nframes);
+    return first;
+}
+
+// The streams of slots 0..nfl-1 into sv, slots 1.. forked from the context's stream.
+int fork_slots(trt_ctx* c, uint32_t want, uint32_t nfl, std::vector<hipStream_t>& sv) {
+    sv.assign(1, c->stream);
+    // every slot's stream is made on first use of the in-flight count, not only the ones this
+    // call needs: creating a stream takes milliseconds and must not land in a later, longer
+    // call (a timed loop after a short warmup)
+    while (c->aux.size() + 1 < want) {
+        hipStream_t s;
+        HIP_TRY(c, hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
+        HIP_TRY(c, trt::touch_stream(s, c->d_counters)); // its hardware queue exists from now on
+        c->aux.push_back(s);
+        hipEvent_t e;
+        HIP_TRY(c, hipEventCreateWithFlags(&e, hipEventDisableTiming));
+        c->aux_ev.push_back(e);
+    }
+    if (nfl > 1) {
+        if (!c->fork_ev) HIP_TRY(c, hipEventCreateWithFlags(&c->fork_ev, hipEventDisableTiming));
+        HIP_TRY(c, hipEventRecord(c->fork_ev, c->stream));
+        for (uint32_t k = 0; k + 1 < nfl; ++k) {
+            HIP_TRY(c, hipStreamWaitEvent(c->aux[k], c->fork_ev, 0));
+            sv.push_back(c->aux[k]);
+        }
+    }
+    return TRT_OK;
+}
+
+int join_slots(trt_ctx* c, uint32_t nfl) {
+    for (uint32_t k = 0; k + 1 < nfl; ++k) {
+        HIP_TRY(c, hipEventRecord(c->aux_ev[k], c->aux[k]));
+        HIP_TRY(c, hipStreamWaitEvent(c->stream, c->aux_ev[k], 0));
+    }
+    return TRT_OK;
 }
 
 } // namespace
@@ -1340,6 +1177,7 @@ int render_frame_list(trt_ctx* c, const trt_params* p, const FrameOut* frames, u
         const trt_view* v = frames[i].view ? frames[i].view : (c->view_on ? &c->view : nullptr);
         return (v && !view_is_identity(*v)) ? v : nullptr;
     };
+    auto ubo_of = [&](uint32_t i) -> const trt_ubo& { return frames[i].ubo ? *frames[i].ubo : c->ubo; };
     bool any_plain_view = false;
     for (uint32_t i = 0; i < nframes; ++i) {
         if (frames[i].view && !view_is_finite(*frames[i].view))
@@ -1350,59 +1188,14 @@ int render_frame_list(trt_ctx* c, const trt_params* p, const FrameOut* frames, u
     A.view_on = any_plain_view ? 0u : 1u;
     if (A.rows != 0 && nframes != 0 && (rc = attach_sky(c, A, false, c->stream)) != TRT_OK) return rc;
     const uint32_t* const sky = A.sky;
-    auto ubo_of = [&](uint32_t i) -> const trt_ubo& { return frames[i].ubo ? *frames[i].ubo : c->ubo; };
     if (A.rows == 0 || nframes == 0) {
         if (nframes) c->ubo = ubo_of(nframes - 1);
         return TRT_OK;
     }
-    // Plain frames (no subtree split, no deferred shadows: the same decision prepare_split
-    // makes) go out several per launch; the others one per launch (per-slot scratch).
-    const bool defer = defer_frame(c, p);
-    const bool split = (defer || !defer_frame(c, p, true)) && split_window(c, p) != 0;
-    const bool plain = !defer && !split;
-    // Frames in flight (main.cpp:45, MAX_FRAMES_IN_FLIGHT): launch j runs on slot j % n.  Slot 0
-    // is the context's stream, slots 1..n-1 are context-owned streams forked from it here and
-    // joined back into it below, so to the caller all frames complete on its stream.  A plain
-    // loop needs no second slot: one multi-frame launch keeps the GPU full from its first frame
-    // to its last, so a 20-frame loop is one launch and drains once (C2 at 20 frames: 20.5 us per
-    // frame against 25.0 with one launch per frame on 4 slots; at 1000 frames 15.6 vs 15.9,
-    // profiles/r03_ab_frame_batch.log); with n slots set explicitly the frames are spread over
-    // n launches.  Per-frame launch sequences (split / deferred-shadow frames) keep the slots
-    // busy instead: auto 4, or defer_in_flight (16) for deferred-shadow frames (8 vs 16 in round
-    // 4: the shipped frame 0.42 -> 0.35 ms, the README scene 0.24 -> 0.17 ms,
-    // profiles/r04z_ab_deferred_in_flight.jsonl; round 2: the shipped frame 1.45 -> 0.56 ms at
-    // 8, profiles/r02_ab_queues_deep.log).
-    uint32_t want = c->frames_in_flight ? c->frames_in_flight : plain ? 1u : defer ? c->defer_in_flight : 4u;
-    // auto: no more deferred slots than device memory holds (each slot owns its scratch)
-    // deferred frames (not split) go out in groups of frames per launch sequence (defer_shape)
-    uint32_t group = 1;
-    if (defer && !split) {
-        uint32_t slots = want;
-        defer_shape(c, group, slots);
-        group = std::min(group, trt::kMaxLaunchFrames);
-        want = slots;
-    }
-    if (!c->frames_in_flight && defer) want = fit_defer_slots(c, p, want, group);
-    const uint32_t cap = plain ? (c->frame_batch ? c->frame_batch : trt::kMaxLaunchFrames) : group;
-    const uint32_t per_launch = std::max(1u, std::min(cap, (nframes + want - 1) / want));
-    // launches: runs of consecutive frames sharing every UBO field but camPos.  Views do not
-    // split launches; a launch with an oriented frame holds at most kMaxViewFrames frames (one
-    // basis each in KArgs::view), so a run breaks where it would outgrow that
-    std::vector<uint32_t> first{0};
-    bool run_oriented = view_of(0) != nullptr;
-    for (uint32_t i = 1; i < nframes; ++i) {
-        const bool o = view_of(i) != nullptr;
-        const uint32_t len = i - first.back();
-        if (len >= per_launch || !same_but_camera(ubo_of(i), ubo_of(first.back())) ||
-            ((run_oriented || o) && len >= trt::kMaxViewFrames)) {
-            first.push_back(i);
-            run_oriented = o;
-        } else {
-            run_oriented = run_oriented || o;
-        }
-    }
-    const uint32_t nl = (uint32_t)first.size();
-    first.push_back(nframes);
+    uint32_t want;
+    const uint32_t per_launch = loop_shape(c, p, nframes, want);
+    const std::vector<uint32_t> first = launch_runs(view_of, ubo_of, nframes, per_launch);
+    const uint32_t nl = (uint32_t)first.size() - 1;
     if (timing) {
         const uint32_t ntimed = (nl + every - 1) / every; // launches 0, every, 2*every, ...
         while (c->fev.size() < 2 * (size_t)ntimed) {
@@ -1413,49 +1206,23 @@ int render_frame_list(trt_ctx* c, const trt_params* p, const FrameOut* frames, u
     }
     uint32_t nfl = std::min(want, nl);
     c->cur_in_flight = nfl;
-    std::vector<hipStream_t> sv{c->stream};
-    // every slot's stream is made on first use of the in-flight count, not only the ones this
-    // call needs: creating a stream takes milliseconds and must not land in a later, longer
-    // call (a timed loop after a short warmup)
-    while (c->aux.size() + 1 < want) {
-        hipStream_t s;
-        HIP_TRY(c, hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
-        HIP_TRY(c, trt::touch_stream(s, c->d_counters)); // its hardware queue exists from now on
-        c->aux.push_back(s);
-        hipEvent_t e;
-        HIP_TRY(c, hipEventCreateWithFlags(&e, hipEventDisableTiming));
-        c->aux_ev.push_back(e);
-    }
-    if (nfl > 1) {
-        if (!c->fork_ev) HIP_TRY(c, hipEventCreateWithFlags(&c->fork_ev, hipEventDisableTiming));
-        HIP_TRY(c, hipEventRecord(c->fork_ev, c->stream));
-        for (uint32_t k = 0; k + 1 < nfl; ++k) {
-            HIP_TRY(c, hipStreamWaitEvent(c->aux[k], c->fork_ev, 0));
-            sv.push_back(c->aux[k]);
-        }
-    }
+    std::vector<hipStream_t> sv;
+    if ((rc = fork_slots(c, want, nfl, sv)) != TRT_OK) return rc;
     for (uint32_t j = 0; j < nl; ++j) {
         const uint32_t i0 = first[j], n = first[j + 1] - i0;
         c->ubo = ubo_of(i0);
         fill_ubo_args(A, c->ubo);
         A.nframes = n;
         for (uint32_t k = 0; k < n; ++k) fill_frame(A.fr[k], ubo_of(i0 + k), frames[i0 + k].out8, frames[i0 + k].in_place);
-        // an oriented launch: no sky table (so no spans, masks or floor class below), and every
+        // an oriented launch: no sky table (so no spans, masks or floor class), and every
         // frame's basis, the identity for its frames of the reference camera
+        const trt_view* views[trt::kMaxLaunchFrames];
         A.view_on = 0;
         for (uint32_t k = 0; k < n; ++k)
-            if (view_of(i0 + k)) A.view_on = 1;
+            if ((views[k] = view_of(i0 + k))) A.view_on = 1;
         A.sky = A.view_on ? nullptr : sky;
-        fill_spans(c, A);
-        if ((rc = attach_smask(c, A, c->stream)) != TRT_OK) return rc;
-        attach_floor_class(c, A);
-        if (A.view_on) { // after the span words: the bases share their bytes (none here: no table)
-            if (n > trt::kMaxViewFrames) return fail(c, TRT_ERR_INVALID, "trt_render_frames: oriented launch too long");
-            for (uint32_t k = 0; k < n; ++k) {
-                const trt_view* v = view_of(i0 + k);
-                fill_view(A, k, v ? *v : kViewIdentity);
-            }
-        }
+        if (A.view_on && n > trt::kMaxViewFrames) return fail(c, TRT_ERR_INVALID, "trt_render_frames: oriented launch too long");
+        if ((rc = prepare_launch(c, A, c->stream, views)) != TRT_OK) return rc;
         uint32_t slot = j % nfl;
         if ((rc = prepare_split(c, p, A, slot, sv[slot])) != TRT_OK) {
             // auto count: a slot whose scratch does not fit in device memory is dropped, with the
@@ -1482,11 +1249,7 @@ int render_frame_list(trt_ctx* c, const trt_params* p, const FrameOut* frames, u
         }
     }
     c->ubo = ubo_of(nframes - 1);
-    for (uint32_t k = 0; k + 1 < nfl; ++k) {
-        HIP_TRY(c, hipEventRecord(c->aux_ev[k], c->aux[k]));
-        HIP_TRY(c, hipStreamWaitEvent(c->stream, c->aux_ev[k], 0));
-    }
-    return TRT_OK;
+    return join_slots(c, nfl);
 }
 
 } // namespace trt
@@ -1553,62 +1316,28 @@ int trt_render(trt_ctx* c, const trt_params* p, uint8_t* out8, float* out32, trt
     KArgs A;
     fill_args(c, p, A);
 
-    if (p->rays_in) {
-        if (dev) {
-            A.rays_in = reinterpret_cast<const float*>(p->rays_in);
-        } else {
-            const size_t bytes = sizeof(trt_ray) * (size_t)p->width * p->height;
-            if ((rc = ensure(c, &c->d_rays, &c->caprays, bytes, "alloc rays")) != TRT_OK) return rc;
-            HIP_TRY(c, hipMemcpyAsync(c->d_rays, p->rays_in, bytes, hipMemcpyHostToDevice, c->stream));
-            A.rays_in = reinterpret_cast<const float*>(c->d_rays);
-        }
+    const float* d_rays = reinterpret_cast<const float*>(p->rays_in);
+    uint32_t* d8 = reinterpret_cast<uint32_t*>(out8);
+    float* d32 = out32;
+    if (!dev) {
+        if (p->rays_in && (rc = stage(c, &c->d_rays, &c->caprays, sizeof(trt_ray) * (size_t)p->width * p->height,
+                                      "alloc rays", p->rays_in, &d_rays)) != TRT_OK)
+            return rc;
+        if (out8 && (rc = stage(c, &c->d_out8, &c->cap8, npx * 4, "alloc rgba8", nullptr, &d8)) != TRT_OK) return rc;
+        if (out32 && (rc = stage(c, &c->d_out32, &c->cap32, npx * 16, "alloc rgba32f", nullptr, &d32)) != TRT_OK) return rc;
     }
-    if (out8) {
-        if (dev) {
-            A.fr[0].out8 = reinterpret_cast<uint32_t*>(out8);
-        } else {
-            if ((rc = ensure(c, &c->d_out8, &c->cap8, npx * 4, "alloc rgba8")) != TRT_OK) return rc;
-            A.fr[0].out8 = reinterpret_cast<uint32_t*>(c->d_out8);
-        }
-    }
-    if (out32) {
-        if (dev) {
-            A.out32 = out32;
-        } else {
-            if ((rc = ensure(c, &c->d_out32, &c->cap32, npx * 16, "alloc rgba32f")) != TRT_OK) return rc;
-            A.out32 = reinterpret_cast<float*>(c->d_out32);
-        }
-    }
+    A.rays_in = d_rays;
+    A.fr[0].out8 = d8;
+    A.out32 = d32;
     if (npx > 0 && (rc = attach_sky(c, A, count, c->stream)) != TRT_OK) return rc;
-    fill_spans(c, A);
-    if ((rc = attach_smask(c, A, c->stream)) != TRT_OK) return rc;
-    attach_floor_class(c, A);
+    if ((rc = prepare_launch(c, A, c->stream, nullptr)) != TRT_OK) return rc;
     const uint32_t slot = render_slot(c, c->stream);
     c->cur_in_flight = 1u; // one frame: its latency is the rate
     if ((rc = prepare_split(c, p, A, slot, c->stream)) != TRT_OK) return rc;
-    if (count) HIP_TRY(c, hipMemsetAsync(c->d_counters, 0, 32 * sizeof(unsigned long long), c->stream));
-    if (timing) HIP_TRY(c, hipEventRecord(c->ev0, c->stream));
+    if ((rc = begin_call(c, count, timing)) != TRT_OK) return rc;
     if (npx > 0) HIP_TRY(c, trt::launch_trace(A, c->stream, count));
     if ((rc = fence_split(c, A, slot, c->stream)) != TRT_OK) return rc;
-    if (timing) HIP_TRY(c, hipEventRecord(c->ev1, c->stream));
-    if (out8 && !dev)
-        HIP_TRY(c, hipMemcpyAsync(out8, c->d_out8, npx * 4, hipMemcpyDeviceToHost, c->stream));
-    if (out32 && !dev)
-        HIP_TRY(c, hipMemcpyAsync(out32, c->d_out32, npx * 16, hipMemcpyDeviceToHost, c->stream));
-    unsigned long long cnt[32] = {0};
-    if (count)
-        HIP_TRY(c, hipMemcpyAsync(cnt, c->d_counters, sizeof(cnt), hipMemcpyDeviceToHost, c->stream));
-    if (!dev || count || timing) HIP_TRY(c, hipStreamSynchronize(c->stream));
-    if (st) {
-        stats_from_counters(st, cnt);
-        st->kernel_ms = 0.0;
-        if (timing) {
-            float ms = 0.0f;
-            HIP_TRY(c, hipEventElapsedTime(&ms, c->ev0, c->ev1));
-            st->kernel_ms = ms;
-        }
-    }
-    return TRT_OK;
+    return finish_call(c, dev, count, timing, st, {{out8, d8, npx * 4}, {out32, d32, npx * 16}});
 }
 
 // Ray queries (abi.h): the caller's rays through ray_query_kernel.  Nothing of the context that a
@@ -1649,15 +1378,9 @@ int trt_trace_rays(trt_ctx* c, const trt_params* p, const trt_qray* rays, uint32
     }
     HIP_TRY(c, hipSetDevice(c->device));
 
-    // what the query reads of p, in a frame-shaped trt_params for fill_args: one row of 64 pixels
-    // stands in for the image (no field of it reaches the kernel)
-    trt_params q;
-    trt_params_default(&q);
-    q.width = 64;
-    q.height = 1;
-    q.max_depth = p->max_depth;
-    q.flags = p->flags & (TRT_FLAG_SPHERES | TRT_FLAG_FLOOR | TRT_FLAG_CHECKER | TRT_FLAG_ENVMAP | TRT_FLAG_BATCH_WALK |
-                          TRT_FLAG_SRGB_OUT | TRT_FLAG_DEVICE_PTRS | TRT_FLAG_COUNT | TRT_FLAG_TIMING);
+    const trt_params q = query_params(p, p->max_depth,
+                                      TRT_FLAG_SPHERES | TRT_FLAG_FLOOR | TRT_FLAG_CHECKER | TRT_FLAG_ENVMAP | TRT_FLAG_BATCH_WALK |
+                                          TRT_FLAG_SRGB_OUT | TRT_FLAG_DEVICE_PTRS | TRT_FLAG_COUNT | TRT_FLAG_TIMING);
     int rc;
     if ((rc = ensure_envp(c, &q, c->stream)) != TRT_OK) return rc;
     KArgs A;
@@ -1670,37 +1393,14 @@ int trt_trace_rays(trt_ctx* c, const trt_params* p, const trt_qray* rays, uint32
     uint4* dh = reinterpret_cast<uint4*>(hits);
     const size_t n = nrays;
     if (!dev) {
-        if ((rc = ensure(c, &c->d_qrays, &c->capqrays, n * sizeof(trt_qray), "alloc query rays")) != TRT_OK) return rc;
-        if (out8 && (rc = ensure(c, &c->d_out8, &c->cap8, n * 4, "alloc rgba8")) != TRT_OK) return rc;
-        if (out32 && (rc = ensure(c, &c->d_out32, &c->cap32, n * 16, "alloc rgba32f")) != TRT_OK) return rc;
-        if (hits && (rc = ensure(c, &c->d_qhits, &c->capqhits, n * sizeof(trt_qhit), "alloc query hits")) != TRT_OK) return rc;
-        HIP_TRY(c, hipMemcpyAsync(c->d_qrays, rays, n * sizeof(trt_qray), hipMemcpyHostToDevice, c->stream));
-        d_rays = static_cast<const float4*>(c->d_qrays);
-        d8 = out8 ? static_cast<uint32_t*>(c->d_out8) : nullptr;
-        d32 = out32 ? static_cast<float4*>(c->d_out32) : nullptr;
-        dh = hits ? static_cast<uint4*>(c->d_qhits) : nullptr;
+        if ((rc = stage(c, &c->d_qrays, &c->capqrays, n * sizeof(trt_qray), "alloc query rays", rays, &d_rays)) != TRT_OK) return rc;
+        if (out8 && (rc = stage(c, &c->d_out8, &c->cap8, n * 4, "alloc rgba8", nullptr, &d8)) != TRT_OK) return rc;
+        if (out32 && (rc = stage(c, &c->d_out32, &c->cap32, n * 16, "alloc rgba32f", nullptr, &d32)) != TRT_OK) return rc;
+        if (hits && (rc = stage(c, &c->d_qhits, &c->capqhits, n * sizeof(trt_qhit), "alloc query hits", nullptr, &dh)) != TRT_OK) return rc;
     }
-    if (count) HIP_TRY(c, hipMemsetAsync(c->d_counters, 0, 32 * sizeof(unsigned long long), c->stream));
-    if (timing) HIP_TRY(c, hipEventRecord(c->ev0, c->stream));
+    if ((rc = begin_call(c, count, timing)) != TRT_OK) return rc;
     HIP_TRY(c, trt::launch_ray_query(A, d_rays, nrays, d8, d32, dh, count, c->stream));
-    if (timing) HIP_TRY(c, hipEventRecord(c->ev1, c->stream));
-    if (!dev) {
-        if (out8) HIP_TRY(c, hipMemcpyAsync(out8, c->d_out8, n * 4, hipMemcpyDeviceToHost, c->stream));
-        if (out32) HIP_TRY(c, hipMemcpyAsync(out32, c->d_out32, n * 16, hipMemcpyDeviceToHost, c->stream));
-        if (hits) HIP_TRY(c, hipMemcpyAsync(hits, c->d_qhits, n * sizeof(trt_qhit), hipMemcpyDeviceToHost, c->stream));
-    }
-    unsigned long long cnt[32] = {0};
-    if (count) HIP_TRY(c, hipMemcpyAsync(cnt, c->d_counters, sizeof(cnt), hipMemcpyDeviceToHost, c->stream));
-    if (!dev || count || timing) HIP_TRY(c, hipStreamSynchronize(c->stream));
-    if (st) {
-        stats_from_counters(st, cnt);
-        if (timing) {
-            float ms = 0.0f;
-            HIP_TRY(c, hipEventElapsedTime(&ms, c->ev0, c->ev1));
-            st->kernel_ms = ms;
-        }
-    }
-    return TRT_OK;
+    return finish_call(c, dev, count, timing, st, {{out8, d8, n * 4}, {out32, d32, n * 16}, {hits, dh, n * sizeof(trt_qhit)}});
 }
 
 // Occlusion queries (abi.h): the caller's segments through occlusion_query_kernel, one byte each.
@@ -1732,13 +1432,7 @@ int trt_occluded(trt_ctx* c, const trt_params* p, const trt_qseg* segs, uint32_t
     }
     HIP_TRY(c, hipSetDevice(c->device));
 
-    // what the query reads of p, in a frame-shaped trt_params for fill_args (as trt_trace_rays)
-    trt_params q;
-    trt_params_default(&q);
-    q.width = 64;
-    q.height = 1;
-    q.max_depth = 1;
-    q.flags = p->flags & (TRT_FLAG_SPHERES | TRT_FLAG_FLOOR | TRT_FLAG_BATCH_WALK | TRT_FLAG_DEVICE_PTRS | TRT_FLAG_TIMING);
+    const trt_params q = query_params(p, 1, TRT_FLAG_SPHERES | TRT_FLAG_FLOOR | TRT_FLAG_BATCH_WALK | TRT_FLAG_DEVICE_PTRS | TRT_FLAG_TIMING);
     int rc;
     KArgs A;
     fill_args(c, &q, A);
@@ -1748,34 +1442,17 @@ int trt_occluded(trt_ctx* c, const trt_params* p, const trt_qseg* segs, uint32_t
     uint8_t* d_out = out;
     const size_t n = nsegs;
     if (!dev) {
-        if ((rc = ensure(c, &c->d_qrays, &c->capqrays, n * sizeof(trt_qseg), "alloc query segments")) != TRT_OK) return rc;
-        if ((rc = ensure(c, &c->d_out8, &c->cap8, n, "alloc occlusion bytes")) != TRT_OK) return rc;
-        HIP_TRY(c, hipMemcpyAsync(c->d_qrays, segs, n * sizeof(trt_qseg), hipMemcpyHostToDevice, c->stream));
-        d_segs = static_cast<const float4*>(c->d_qrays);
-        d_out = reinterpret_cast<uint8_t*>(c->d_out8);
+        if ((rc = stage(c, &c->d_qrays, &c->capqrays, n * sizeof(trt_qseg), "alloc query segments", segs, &d_segs)) != TRT_OK) return rc;
+        if ((rc = stage(c, &c->d_out8, &c->cap8, n, "alloc occlusion bytes", nullptr, &d_out)) != TRT_OK) return rc;
     }
-    if (timing) HIP_TRY(c, hipEventRecord(c->ev0, c->stream));
+    if ((rc = begin_call(c, false, timing)) != TRT_OK) return rc;
     HIP_TRY(c, trt::launch_occlusion_query(A, d_segs, nsegs, d_out, c->stream));
-    if (timing) HIP_TRY(c, hipEventRecord(c->ev1, c->stream));
-    if (!dev) HIP_TRY(c, hipMemcpyAsync(out, c->d_out8, n, hipMemcpyDeviceToHost, c->stream));
-    if (!dev || timing) HIP_TRY(c, hipStreamSynchronize(c->stream));
-    if (timing) {
-        float ms = 0.0f;
-        HIP_TRY(c, hipEventElapsedTime(&ms, c->ev0, c->ev1));
-        st->kernel_ms = ms;
-    }
-    return TRT_OK;
+    return finish_call(c, dev, false, timing, st, {{out, d_out, n}});
 }
 
 } // extern "C"
 
 // ---- envmap JPEG: host entropy decode + GPU reconstruction ----------------
-
-namespace trt {
-namespace jpeg {
-const Image* image_of(const trt_jpeg* j);
-}
-} // namespace trt
 
 extern "C" int trt_jpeg_decode(trt_ctx* c, const trt_jpeg* j, uint8_t* out, uint32_t flags) {
     if (!c) return TRT_ERR_INVALID;
@@ -1784,213 +1461,13 @@ extern "C" int trt_jpeg_decode(trt_ctx* c, const trt_jpeg* j, uint8_t* out, uint
     if (!out) return fail(c, TRT_ERR_INVALID, "trt_jpeg_decode: null output");
     HIP_TRY(c, hipSetDevice(c->device));
     const size_t bytes = (size_t)im->width * im->height * 4;
+    const bool dev = (flags & TRT_FLAG_DEVICE_PTRS) != 0;
     uint8_t* dst = out;
-    if (!(flags & TRT_FLAG_DEVICE_PTRS)) {
-        int rc = ensure(c, &c->d_out8, &c->cap8, bytes, "jpeg output");
+    if (!dev) {
+        const int rc = stage(c, &c->d_out8, &c->cap8, bytes, "jpeg output", nullptr, &dst);
         if (rc != TRT_OK) return rc;
-        dst = static_cast<uint8_t*>(c->d_out8);
     }
     HIP_TRY(c, trt::jpeg::reconstruct(*im, dst, c->stream));
-    if (!(flags & TRT_FLAG_DEVICE_PTRS)) {
-        HIP_TRY(c, hipMemcpyAsync(out, dst, bytes, hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(c, hipStreamSynchronize(c->stream));
-    }
-    return TRT_OK;
+    return finish_call(c, dev, false, false, nullptr, {{out, dst, bytes}});
 }
 
-extern "C" int trt_upload_envmap_jpeg(trt_ctx* c, const uint8_t* data, size_t len) {
-    if (!c) return TRT_ERR_INVALID;
-    trt_jpeg* j = nullptr;
-    int rc = trt_jpeg_create(&j);
-    if (rc != TRT_OK) return fail(c, rc, "trt_upload_envmap_jpeg: out of memory");
-    rc = trt_jpeg_parse(j, data, len);
-    if (rc != TRT_OK) {
-        std::string msg = std::string("trt_upload_envmap_jpeg: ") + trt_jpeg_last_error(j);
-        trt_jpeg_destroy(j);
-        return fail(c, rc, msg);
-    }
-    const trt::jpeg::Image* im = trt::jpeg::image_of(j);
-    hipError_t e = hipSetDevice(c->device);
-    uint32_t* d = nullptr;
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&d), (size_t)im->width * im->height * 4);
-    if (e == hipSuccess) e = trt::jpeg::reconstruct(*im, reinterpret_cast<uint8_t*>(d), c->stream);
-    if (e != hipSuccess) {
-        (void)hipFree(d);
-        trt_jpeg_destroy(j);
-        return hip_fail(c, e, "trt_upload_envmap_jpeg");
-    }
-    (void)hipFree(c->d_env);
-    c->d_env = d;
-    c->envp_ok = false;
-    ++c->env_gen;
-    c->env_w = (uint32_t)im->width;
-    c->env_h = (uint32_t)im->height;
-    c->scene_bytes[trt::kSceneEnv] = (size_t)im->width * im->height * 4;
-    trt_jpeg_destroy(j);
-    return TRT_OK;
-}
-
-// ---- scene export / adoption (the RCCL scene broadcast of trt_multi.cpp) --------------------
-
-namespace trt {
-
-void** scene_buf(trt_ctx* c, int k) {
-    switch (k) {
-    case kSceneBatches: return reinterpret_cast<void**>(&c->d_batches);
-    case kSceneNodes: return reinterpret_cast<void**>(&c->d_nodes);
-    case kSceneBvh: return reinterpret_cast<void**>(&c->d_bvh);
-    case kSceneBvh4: return reinterpret_cast<void**>(&c->d_bvh4);
-    case kSceneBvhTris: return reinterpret_cast<void**>(&c->d_bvh_tris);
-    case kSceneGeo: return reinterpret_cast<void**>(&c->d_geo);
-    case kSceneShade: return reinterpret_cast<void**>(&c->d_shade);
-    case kSceneMats: return reinterpret_cast<void**>(&c->d_mats);
-    case kSceneBvh4Q: return reinterpret_cast<void**>(&c->d_bvh4q);
-    default: return reinterpret_cast<void**>(&c->d_env);
-    }
-}
-
-void scene_header(const trt_ctx* c, SceneHeader& h) {
-    std::memset(&h, 0, sizeof(h));
-    h.magic = kSceneMagic;
-    h.nbatch = c->nbatch;
-    h.ntri = c->ntri;
-    h.nmat = c->nmat;
-    h.env_w = c->env_w;
-    h.env_h = c->env_h;
-    h.top = c->top;
-    std::memcpy(h.node_off, c->node_off, sizeof(h.node_off));
-    for (int k = 0; k < kSceneBufs; ++k) h.bytes[k] = c->scene_bytes[k];
-    h.ubo = c->ubo;
-}
-
-int scene_adopt(trt_ctx* c, const SceneHeader& h) {
-    if (h.magic != kSceneMagic) return fail(c, TRT_ERR_INVALID, "scene broadcast: bad header");
-    HIP_TRY(c, hipSetDevice(c->device));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    free_scene(c);
-    for (int k = 0; k < kSceneBufs; ++k) {
-        if (!h.bytes[k]) continue;
-        void** p = scene_buf(c, k);
-        hipError_t e = hipMalloc(p, h.bytes[k]);
-        if (e != hipSuccess) {
-            free_scene(c);
-            return hip_fail(c, e, "scene broadcast: alloc");
-        }
-        c->scene_bytes[k] = h.bytes[k];
-    }
-    c->nbatch = h.nbatch;
-    c->ntri = h.ntri;
-    c->nmat = h.nmat;
-    c->env_w = h.env_w;
-    c->env_h = h.env_h;
-    c->top = h.top;
-    std::memcpy(c->node_off, h.node_off, sizeof(c->node_off));
-    c->ubo = h.ubo;
-    c->have_scene = true;
-    return TRT_OK;
-}
-
-} // namespace trt
-
-// ---- diagnostics (not part of include/trt/abi.h; tools/shadow_exp.py) ----------------------
-
-// Ray-dump buffer of TRT_DIAG_DUMP_SHADOW builds (device pointer, or NULL).
-// diagnostic: the first 16 words of slot `slot`'s deferred-frame counters (nfb + pad, where
-// defer_resolve records a log it could not finish)
-extern "C" int trt_diag_defer_pad(trt_ctx* c, uint32_t slot, uint32_t* out16) {
-    if (!c || !out16 || slot >= TRT_BUILD_MAX_IN_FLIGHT || !c->split[slot].dctr) return TRT_ERR_INVALID;
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    HIP_TRY(c, hipMemcpy(out16, c->split[slot].dctr, 16 * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    return TRT_OK;
-}
-
-extern "C" int trt_diag_set_buffer(trt_ctx* c, void* dev_ptr) {
-    if (!c) return TRT_ERR_INVALID;
-    c->diag = dev_ptr;
-    return TRT_OK;
-}
-
-// attach_floor_class's floor_lit conditions on a launch's flags and its three lights (x, y, z
-// each), without the knob: 1 or 0 (tests/test_floor_lit.py, no GPU).
-extern "C" int trt_diag_floor_lit(uint32_t flags, const float* lights) {
-    if (!lights) return 0;
-    return (int)floor_lit(flags, reinterpret_cast<const float(*)[3]>(lights));
-}
-
-// counters[k] of the last counting pass (k < 32).
-extern "C" unsigned long long trt_diag_counter(trt_ctx* c, uint32_t k) {
-    unsigned long long v = 0;
-    if (!c || k >= 32 || hipSetDevice(c->device) != hipSuccess) return 0;
-    if (hipMemcpy(&v, c->d_counters + k, sizeof(v), hipMemcpyDeviceToHost) != hipSuccess) return 0;
-    return v;
-}
-
-// Traces n shadow queries (2 float4 each, device) into occ (device, one uint32 each) on the
-// context's stream with the frame params' traversal (BVH build, waves).
-extern "C" int trt_diag_shadow_batch(trt_ctx* c, const trt_params* p, const void* rays, uint32_t n, void* occ) {
-    if (!c) return TRT_ERR_INVALID;
-    int rc = check_params(c, p);
-    if (rc != TRT_OK) return rc;
-    HIP_TRY(c, hipSetDevice(c->device));
-    if ((rc = ensure_envp(c, p, c->stream)) != TRT_OK) return rc;
-    KArgs A;
-    fill_args(c, p, A);
-    HIP_TRY(c, trt::launch_shadow_batch(A, static_cast<const float4*>(rays), n, static_cast<uint32_t*>(occ), c->stream));
-    return TRT_OK;
-}
-
-// Diagnostic (tests/test_bvh_layout.py): the BVH2 the upload builds — nodes and the BVH-ordered
-// leaf triangle records (meta: triangle, batch, ni) — copied out when the capacities suffice;
-// counts[0] = nodes, counts[1] = leaf references.
-extern "C" int trt_diag_bvh_export(const trt_triangle* tris, uint32_t ntri, const trt_model* models, uint32_t nmodel,
-                                   trt::BvhNode* nodes_out, uint32_t cap_nodes, TriGeo* tris_out, uint32_t cap_tris,
-                                   uint64_t counts[2]) {
-    if (!counts || (ntri && !tris) || (nmodel && !models)) return TRT_ERR_INVALID;
-    std::vector<trt::BvhNode> bvh;
-    std::vector<TriGeo> bvh_tris;
-    if (!nmodel || !trt::build_bvh(tris, ntri, models, nmodel, bvh, bvh_tris)) return TRT_ERR_INVALID;
-    counts[0] = bvh.size();
-    counts[1] = bvh_tris.size();
-    if (nodes_out && bvh.size() <= cap_nodes) std::memcpy(nodes_out, bvh.data(), bvh.size() * sizeof(trt::BvhNode));
-    if (tris_out && bvh_tris.size() <= cap_tris) std::memcpy(tris_out, bvh_tris.data(), bvh_tris.size() * sizeof(TriGeo));
-    return TRT_OK;
-}
-
-// Diagnostic (tests/test_mesh_cases.py), host only: the 4-wide nodes collapse_bvh4 makes of that
-// BVH2 (child refs index these nodes or the leaf references of trt_diag_bvh_export), copied out
-// when the capacity suffices; counts[0] = 4-wide nodes, counts[1] = their worst-case stack (the
-// upload keeps them only when it is <= kBvhStack).
-extern "C" int trt_diag_bvh4_export(const trt_triangle* tris, uint32_t ntri, const trt_model* models, uint32_t nmodel,
-                                    trt::Bvh4Node* nodes_out, uint32_t cap_nodes, uint64_t counts[2]) {
-    if (!counts || (ntri && !tris) || (nmodel && !models)) return TRT_ERR_INVALID;
-    std::vector<trt::BvhNode> bvh;
-    std::vector<TriGeo> bvh_tris;
-    if (!nmodel || !trt::build_bvh(tris, ntri, models, nmodel, bvh, bvh_tris)) return TRT_ERR_INVALID;
-    std::vector<trt::Bvh4Node> bvh4;
-    counts[1] = trt::collapse_bvh4(bvh, bvh4);
-    counts[0] = bvh4.size();
-    if (nodes_out && bvh4.size() <= cap_nodes) std::memcpy(nodes_out, bvh4.data(), bvh4.size() * sizeof(trt::Bvh4Node));
-    return TRT_OK;
-}
-
-// Host-only check of the BVH pipeline of trt_upload_scene (no GPU): BVH2 build, 4-wide
-// collapse and quantization.  out[0] BVH2 nodes, out[1] BVH4 nodes, out[2] quantized (0/1),
-// out[3] BVH2 depth (levels of the deepest leaf, root = 1), out[4] worst-case BVH4 stack,
-// out[5] leaf triangles.  Returns TRT_ERR_INVALID when no BVH is built (overlapping batch ranges).
-extern "C" int trt_diag_bvh_build(const trt_triangle* tris, uint32_t ntri, const trt_model* models, uint32_t nmodel,
-                                  uint64_t out[6]) {
-    if (!out || (ntri && !tris) || (nmodel && !models)) return TRT_ERR_INVALID;
-    for (int i = 0; i < 6; ++i) out[i] = 0;
-    std::vector<trt::BvhNode> bvh;
-    std::vector<TriGeo> bvh_tris;
-    if (!nmodel || !trt::build_bvh(tris, ntri, models, nmodel, bvh, bvh_tris)) return TRT_ERR_INVALID;
-    std::vector<trt::Bvh4Node> bvh4;
-    out[0] = bvh.size();
-    out[4] = trt::collapse_bvh4(bvh, bvh4);
-    out[1] = bvh4.size();
-    std::vector<trt::Bvh4QNode> q;
-    out[2] = (!bvh4.empty() && trt::quantize_bvh4(bvh4, q)) ? 1 : 0;
-    out[3] = trt::bvh_depth(bvh);
-    out[5] = bvh_tris.size();
-    return TRT_OK;
-}
