@@ -14,6 +14,7 @@
 #include <hip/hip_runtime.h>
 
 #include "sky_spans.h"
+#include "trt_deal.h"
 
 namespace trt {
 
@@ -291,6 +292,9 @@ struct KArgs {
     // checker) and every light lies above its plane by more than kFloorLitPad (attach_floor_class).
     uint32_t floor_class;
     uint32_t view_on;
+    // Tile dealing (trt_deal.h): the launch's constants and magic divisors, filled once per launch
+    // on the host (fill_args; prepare_launch once the launch's frames are known).
+    Deal deal;
 };
 constexpr uint32_t kFloorLit = 2u;     // KArgs::floor_class
 constexpr float kFloorLitPad = 1e-2f; // the shadow masks' pad above the floor plane y = -4

@@ -51,6 +51,52 @@ extern "C" int trt_diag_shadow_batch(trt_ctx* c, const trt_params* p, const void
     return TRT_OK;
 }
 
+// Diagnostic (tests/test_deal_order.py), host only: the (tile, frame) of every block of a launch
+// shape, by the kernels' own dealing functions (trt_deal.h) over fill_deal's constants.
+// inter 0: block vb is xcd_tile(vb % ntiles, vb / ntiles) (F frames one after the other; F 1: a
+// single frame); inter 1, 2: inter_tile over F frames or pairs.  tile_out, frame_out: ntiles * F
+// words each.
+extern "C" int trt_diag_deal_map(uint32_t ntx, uint32_t ntiles, uint32_t F, uint32_t xcd_rot, uint32_t xcd_skew,
+                                 uint32_t xcd_inter, uint32_t xcd_mult, uint32_t* tile_out, uint32_t* frame_out) {
+    if (!ntx || !ntiles || ntiles % ntx || !F || !tile_out || !frame_out) return TRT_ERR_INVALID;
+    Deal D;
+    fill_deal(D, ntx, ntiles, xcd_inter ? F : 1u);
+    const DealKnobs K{xcd_rot, xcd_skew, xcd_inter, xcd_mult};
+    for (uint32_t vb = 0; vb < ntiles * F; ++vb) {
+        uint32_t f = 0, tile;
+        if (xcd_inter) {
+            tile = inter_tile(D, K, vb, f);
+        } else {
+            f = vb / ntiles;
+            tile = xcd_tile(D, K, vb - f * ntiles, f);
+        }
+        tile_out[vb] = tile;
+        frame_out[vb] = f;
+    }
+    return TRT_OK;
+}
+
+// Diagnostic, host only: the kernels' division by a launch divisor (trt_deal.h deal_div over
+// deal_magic's multiplier).  trt_diag_deal_div: out[i] = n[i] / d by deal_div; trt_diag_deal_div_range:
+// the number of n in [n0, n1) for which deal_div differs from n / d.
+extern "C" void trt_diag_deal_div(uint32_t d, const uint32_t* n, uint32_t count, uint32_t* out) {
+    Deal D{};
+    uint32_t s;
+    deal_magic(d, D.magic[kDivNl], s);
+    D.shifts = s << (6u * kDivNl);
+    for (uint32_t i = 0; i < count; ++i) out[i] = deal_div(D, kDivNl, n[i]);
+}
+extern "C" uint64_t trt_diag_deal_div_range(uint32_t d, uint64_t n0, uint64_t n1) {
+    if (!d || n1 > (1ull << 32)) return UINT64_MAX;
+    Deal D{};
+    uint32_t s;
+    deal_magic(d, D.magic[kDivNtx], s);
+    D.shifts = s;
+    uint64_t bad = 0;
+    for (uint64_t n = n0; n < n1; ++n) bad += deal_div(D, kDivNtx, (uint32_t)n) != (uint32_t)n / d;
+    return bad;
+}
+
 namespace {
 // The upload's BVH step, 4-wide nodes kept whatever their stack.  False: bad arguments or no BVH.
 bool diag_bvh(const trt_triangle* tris, uint32_t ntri, const trt_model* models, uint32_t nmodel, const void* out,

@@ -2278,10 +2278,10 @@ __device__ __forceinline__ void store_pixel_grey(const KArgs& A, const FrameRec&
 // are wave-uniform, so this is scalar work and one scalar load from the kernel arguments.
 __device__ __forceinline__ uint32_t span_word(const KArgs& A, uint32_t tile, uint32_t f) {
     if (A.span_tables == 0u || tile >= A.ntiles) return kSpanFull;
-    return A.span[(f >> A.span_shift) * A.span_ntr + tile / A.ntx];
+    return A.span[(f >> A.span_shift) * A.span_ntr + deal_div(A.deal, kDivNtx, tile)];
 }
 __device__ __forceinline__ bool span_outside(const KArgs& A, uint32_t tile, uint32_t span) {
-    const uint32_t col = tile % A.ntx;
+    const uint32_t col = tile - deal_div(A.deal, kDivNtx, tile) * A.ntx;
     return col < (span & 0xffffu) || col >= (span >> 16);
 }
 
@@ -2290,7 +2290,8 @@ __device__ __forceinline__ bool span_outside(const KArgs& A, uint32_t tile, uint
 // primary ray generated or intersected.
 __device__ __forceinline__ void sky_tile_store(const KArgs& A, uint32_t tile, const FrameRec& F0, const FrameRec* F1) {
     const uint32_t lane = lane_id();
-    const uint32_t x = (tile % A.ntx) * 8u + (lane & 7u), k = (tile / A.ntx) * 8u + (lane >> 3);
+    const uint32_t trow = deal_div(A.deal, kDivNtx, tile); // the launch's magic divisor (trt_deal.h)
+    const uint32_t x = (tile - trow * A.ntx) * 8u + (lane & 7u), k = trow * 8u + (lane >> 3);
     if (x >= A.width || k >= A.rows) return;
     const uint32_t word = A.sky[(size_t)band_row(A, k) * A.width + x];
     const size_t o = (size_t)k * A.width + x;
@@ -2302,7 +2303,7 @@ __device__ __forceinline__ void sky_tile_store(const KArgs& A, uint32_t tile, co
 // floor_pack words, c0 | c1 << 8 | s0 << 16 | s1 << 24 (sky_spans.h).
 __device__ __forceinline__ uint32_t floor_span_word(const KArgs& A, uint32_t tile, uint32_t f) {
     if (tile >= A.ntiles) return kFloorPackFull;
-    return A.span[(f >> A.span_shift) * A.span_ntr + tile / A.ntx];
+    return A.span[(f >> A.span_shift) * A.span_ntr + deal_div(A.deal, kDivNtx, tile)];
 }
 __device__ __forceinline__ bool floor_span_outside(uint32_t col, uint32_t w) {
     return col < (w & 0xffu) || col >= ((w >> 8) & 0xffu);
@@ -2593,86 +2594,13 @@ __device__ __forceinline__ void trace_samples(const KArgs& A, const FrameRec& F,
     store_pixel(A, F, (size_t)k * A.width + x, acc);
 }
 
-// Blocks b and b+8 share an XCD (round-robin dispatch, MI355X_MICROARCH.md): give each XCD
-// 2x2-tile chunks (16x16 px) so neighbouring pixels' envmap texels and batch records hit
-// the same XCD L2.  Chunk c of XCD x is global chunk c*8+x; chunks are row-major over the
-// image in 2x2 tile units.  Bijective on [0, ntiles) (tail tiles map to themselves).
-//
-// Frame f of a multi-frame launch can deal the chunk classes rotated (xcd_rot: class
-// (x + f / 2^(xcd_rot - 1)) mod 8 to XCD x) and skewed per chunk row (xcd_skew: row cy's chunk
-// columns shifted by xcd_skew * cy, diagonal classes).  Both are bijections of the chunks, so
-// every tile is traced once; they only move work between XCDs.  Why: the hardware deals blocks
-// to the XCDs round-robin, statically, so an XCD whose chunk class is costlier (the glass
-// spheres' stripes) finishes its share of a launch later than the others.
-// perm (xcd_inter 2): chunk k of the evenly dealt ones is chunk (k * xcd_mult) mod nfull, a
-// bijection (xcd_mult is coprime to nfull) that makes each XCD's chunks a 2-D lattice spread over
-// the whole image instead of every 8th chunk column.
-__device__ __forceinline__ uint32_t xcd_deal(const KArgs& A, uint32_t b, uint32_t roff, bool perm = false) {
-    const uint32_t tyn = A.ntiles / A.ntx;
-    const uint32_t cw = A.ntx / 2u, ch = tyn / 2u;                 // whole 2x2 chunks
-    const uint32_t nchunk = cw * ch, nfull = (nchunk / 8u) * 8u;   // dealt evenly to the XCDs
-    auto chunk_tile = [&](uint32_t chunk, uint32_t sub) {
-        uint32_t cx = chunk % cw;
-        const uint32_t cy = chunk / cw;
-        if (A.xcd_skew) cx = (cx + A.xcd_skew * cy) % cw;
-        return (cy * 2u + sub / 2u) * A.ntx + cx * 2u + (sub % 2u);
-    };
-    if (b < nfull * 4u) {
-        const uint32_t j = b / 8u; // j-th block of XCD x
-        uint32_t x = b % 8u;
-        x = (x + roff) & 7u;
-        uint32_t k = (j / 4u) * 8u + x;
-        if (perm) k = (k * A.xcd_mult) % nfull; // fits 32 bits: the host keeps xcd_mult 1 for >= 65536 chunks
-        return chunk_tile(k, j % 4u);
-    }
-    // leftovers: the last nchunk % 8 chunks, then the odd right column, then the odd bottom row
-    uint32_t r = b - nfull * 4u;
-    const uint32_t nc = (nchunk - nfull) * 4u;
-    if (r < nc) return chunk_tile(nfull + r / 4u, r % 4u);
-    r -= nc;
-    const uint32_t na = (A.ntx & 1u) ? ch * 2u : 0u;
-    if (r < na) return r * A.ntx + (A.ntx - 1u);
-    r -= na;
-    return (ch * 2u) * A.ntx + r; // tile rows odd: the last tile row
+// The dealing of blocks to tiles and frames lives in trt_deal.h (xcd_deal, xcd_tile, xcd_tile_base,
+// inter_tile over KArgs::deal); these read the launch's knobs beside it.
+__device__ __forceinline__ DealKnobs deal_knobs(const KArgs& A) {
+    return DealKnobs{A.xcd_rot, A.xcd_skew, A.xcd_inter, A.xcd_mult};
 }
-
-// Block b's tile with the chunk classes rotated for frame f of this launch (xcd_rot: by
-// f / 2^(xcd_rot - 1)).  Successive single-frame launches keep one dealing: rotating them too
-// (a per-launch offset) cost the shipped frame's 8 in-flight deferred frames +5 % (consecutive
-// frames' tiles on one XCD share its L2) for README -2 %, profiles/r03_ab_launch_off.log.
 __device__ __forceinline__ uint32_t xcd_tile(const KArgs& A, uint32_t b, uint32_t f = 0) {
-    return xcd_deal(A, b, A.xcd_rot ? (f >> (A.xcd_rot - 1u)) : 0u);
-}
-// the unrotated dealing
-__device__ __forceinline__ uint32_t xcd_tile_base(const KArgs& A, uint32_t b) { return xcd_deal(A, b, 0u); }
-
-// Frame-interleaved dealing of a multi-frame launch (xcd_inter): the launch walks the chunk
-// groups once, and each XCD traces chunk group g of every frame before group g + 1 (frame f's
-// chunk of group g rotated by f, so every XCD sees every chunk class).  All frames advance
-// together, so the launch ends on the last chunk groups of all frames instead of on the last
-// frame's whole tile order (whose costliest tiles then start near the end).  Sets f; tiles
-// outside whole chunk groups (leftovers) are dealt frame by frame after them.
-// F: the launch's frames (or frame pairs, frame_pair).
-// xcd_inter 2: no rotation — chunk group g's chunk on XCD x is the same in every frame of the
-// launch, so that XCD traces that chunk in all frames back to back and the texels its primary
-// rays miss into (the same directions in every frame while the camera only translates) stay in its L2;
-// the permuted classes (xcd_deal perm) keep the XCDs balanced without the rotation.
-__device__ __forceinline__ uint32_t inter_tile(const KArgs& A, uint32_t vb, uint32_t& f, uint32_t F) {
-    const uint32_t tyn = A.ntiles / A.ntx;
-    const uint32_t nchunk = (A.ntx / 2u) * (tyn / 2u), nfull = (nchunk / 8u) * 8u;
-    const uint32_t per = nfull * 4u; // blocks per frame in whole chunk groups
-    if (vb < F * per) {
-        const uint32_t x = vb % 8u, i = vb / 8u, q = i / 4u;
-        f = q % F;
-        const uint32_t g = q / F; // chunk group: chunks g * 8 .. g * 8 + 7
-        // block (g * 8 + ((x + f) & 7)) * 4 + i % 4 of frame f, in xcd_tile's unrotated dealing
-        const bool fixed = A.xcd_inter == 2u;
-        const uint32_t c = fixed ? x : (x + f) & 7u;
-        return xcd_deal(A, (g * 4u + i % 4u) * 8u + c, 0u, fixed);
-    }
-    const uint32_t r = vb - F * per, nl = A.ntiles - per;
-    f = r / nl;
-    return xcd_tile_base(A, per + r % nl);
+    return xcd_tile(A.deal, deal_knobs(A), b, f);
 }
 
 // One 64-lane workgroup per 8x8 tile.  The hardware dispatcher hands each freed wave slot
@@ -2685,17 +2613,11 @@ __device__ __forceinline__ uint32_t inter_tile(const KArgs& A, uint32_t vb, uint
 #ifndef TRT_WAVES
 #define TRT_WAVES 1
 #endif
-// Frame pairs (TRT_FRAME_GROUP=2) for mesh frames: compiled only on request (measured slower
-// for meshes: C4 +2.5 %, C3 +10 %, profiles/r03_ab_frame_pair.log)
-#ifndef TRT_MESH_PAIRS
-#define TRT_MESH_PAIRS 0
-#endif
 // Whether a plain launch of more than one frame deals its blocks as frame pairs: one definition
-// for the host's grid size (launch_trace: half the blocks) and the kernel's dealing (trace_body,
-// with its GEOM).  Triangle-free frames only unless TRT_MESH_PAIRS: mesh kernels do not compile
-// the pair path.
+// (trt_deal.h deal_pairs) for the host's grid size (launch_trace: half the blocks), the host's
+// dealing constants (deal_frames) and the kernel's dealing (trace_body, with its GEOM).
 __host__ __device__ __forceinline__ bool pairs_launch(const KArgs& A, int geom) {
-    return A.xcd_inter && A.frame_group > 1u && (geom == 0 || TRT_MESH_PAIRS);
+    return deal_pairs(A.xcd_inter, A.frame_group, geom == 0);
 }
 
 __device__ __forceinline__ void flush_counts(const KArgs& A, const Cnt& cnt) {
@@ -2783,7 +2705,7 @@ __device__ __forceinline__ void trace_body(const KArgs& A) {
             // 8.60 -> 9.13, and 8.67 with the loop's hoisted kernel arguments kept out of the
             // registers: profiles/one_body_ab_summary.txt)
             uint32_t pr;
-            tile = inter_tile(A, vb, pr, (A.nframes + 1u) / 2u);
+            tile = inter_tile(A.deal, deal_knobs(A), vb, pr); // deal.F: the pairs
             f = 2u * pr;
             if constexpr (SKY) { // a pair never straddles two span tables (span_shift >= 1)
                 pair = true;
@@ -2796,7 +2718,7 @@ __device__ __forceinline__ void trace_body(const KArgs& A) {
                 return;
             }
         } else if (A.xcd_inter) {
-            tile = inter_tile(A, vb, f, A.nframes);
+            tile = inter_tile(A.deal, deal_knobs(A), vb, f); // deal.F: the frames
         } else {
             f = vb / A.ntiles;
             t = vb - f * A.ntiles;
@@ -2851,7 +2773,7 @@ __device__ __forceinline__ void trace_body(const KArgs& A) {
     constexpr bool cull = true;
 #endif
     if constexpr (FLOORC) {
-        const uint32_t w = floor_span_word(A, tile, f), col = tile % A.ntx;
+        const uint32_t w = floor_span_word(A, tile, f), col = tile - deal_div(A.deal, kDivNtx, tile) * A.ntx;
         if (cull && floor_span_outside(col, w)) {
             sky_tile_store(A, tile, A.fr[f], nf > 1u ? &A.fr[f + 1u] : nullptr);
             return;
@@ -3470,6 +3392,11 @@ hipError_t launch_trace(const KArgs& A, hipStream_t stream, bool count) {
                              : A.nframes > 1u && pairs_launch(A, geom) ? (A.nframes + 1u) / 2u
                                                                        : std::max(A.nframes, 1u);
     const dim3 fgrid(A.ntiles * fblocks);
+    // the kernels deal their blocks by the host's constants (fill_args, prepare_launch): a launch
+    // whose constants are not those of its own shape is an error, never a wrong image
+    if (A.deal.ntx != A.ntx || A.deal.nl + A.deal.per != A.ntiles ||
+        (!A.spp_lanes && A.deal.F != deal_frames(A.nframes, A.xcd_inter, A.frame_group, geom == 0)))
+        return hipErrorInvalidValue;
     // the sky table's kernel: what the host's conditions (attach_sky) promise, checked again
     const bool sky = A.sky && geom == 0 && !count && A.spp <= 1 && !A.rays_in && !A.out32;
     dispatch_geom(geom, [&](auto g) {

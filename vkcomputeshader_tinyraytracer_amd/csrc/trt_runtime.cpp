@@ -521,6 +521,8 @@ void fill_args(trt_ctx* c, const trt_params* p, KArgs& A) {
     // vary more from frame to frame and a pair doubles the longest wave),
     // profiles/r03_ab_frame_pair.log
     A.frame_group = c->frame_group > 0 ? (uint32_t)c->frame_group : (c->nbatch == 0 ? 2u : 1u);
+    // the dealing constants of a single frame; prepare_launch writes those of the launch's frames
+    trt::fill_deal(A.deal, A.ntx, A.ntiles, 1u);
 }
 
 } // namespace trt
@@ -695,6 +697,12 @@ void attach_floor_class(const trt_ctx* c, KArgs& A) {
     if (c->floor_lit_on && floor_lit(A.flags, A.light)) A.floor_class |= trt::kFloorLit;
 }
 
+// The dealing constants of a launch (KArgs::deal, trt_deal.h), once its frames are set: the frames
+// or pairs its kernel interleaves.
+void attach_deal(KArgs& A) {
+    trt::fill_deal(A.deal, A.ntx, A.ntiles, trt::deal_frames(A.nframes, A.xcd_inter, A.frame_group, A.nbatch == 0));
+}
+
 // Launch preparation, once the frames, the UBO, A.sky and A.view_on are set.  The order is a
 // correctness condition: the floor class needs the masks and repacks A.span in place from
 // c->sph_span, which fill_spans left behind; the bases of an oriented launch (views[f], null: the
@@ -705,6 +713,7 @@ int prepare_launch(trt_ctx* c, KArgs& A, hipStream_t stream, const trt_view* con
     const int rc = attach_smask(c, A, stream);
     if (rc != TRT_OK) return rc;
     attach_floor_class(c, A);
+    attach_deal(A);
     if (A.view_on && views)
         for (uint32_t f = 0; f < A.nframes; ++f) fill_view(A, f, views[f] ? *views[f] : kViewIdentity);
     return TRT_OK;
