@@ -413,6 +413,71 @@ int trt_occluded(trt_ctx* ctx, const trt_params* p, const trt_qseg* segs, uint32
  * bad index in *first_bad (may be NULL).  segs NULL with n > 0 is TRT_ERR_INVALID (*first_bad = 0). */
 int trt_check_segs(const trt_qseg* segs, uint32_t n, uint32_t* first_bad);
 
+/* ---- visibility masks: any hit over a direction or target set per point ----------------------
+ * The gather form of the occlusion query.  Ambient occlusion, light visibility and form-factor
+ * sampling come as POINTS that each ask the same K questions: K hemisphere directions from a
+ * surface point, or the scene's lights from every hit.  Through trt_occluded the caller expands
+ * every point into K 32-byte segments and reads K bytes back; here the points go in (32 B each),
+ * the set of K <= TRT_VIS_MAX_SET directions or targets is shared by all of them, the segments are
+ * made in the kernel, and one 64-bit mask per point comes out: bit k = segment (i, k) is occluded.
+ *
+ * `set` is always a HOST array of nset entries of 4 floats each (the 4th is ignored), copied during
+ * the call; 1 <= nset <= TRT_VIS_MAX_SET.  Segment (i, k) is built from point i and entry e =
+ * set[k], all in FP32, every product and sum rounded on its own, in the project's dot order, no FMA:
+ *   TRT_VIS_DIRS:     s = (e.x * n.x + e.y * n.y) + e.z * n.z;  dir = s < 0 ? -e : e (zero, -0.0 and
+ *                     n = (0,0,0) keep e: a zero normal means "the whole sphere, no flip");  org =
+ *                     pos;  tmax = the point's.  n only chooses a side and need not be normalized.
+ *   TRT_VIS_TARGETS:  dir = e.xyz - pos, componentwise;  len = sqrt((dx*dx + dy*dy) + dz*dz),
+ *                     correctly rounded;  tmax = fminf(len, the point's tmax): the point's tmax is a
+ *                     range cap.  n is not read.
+ * Bit k of out_masks[i] is 1 iff trt_occluded would report TRT_OCC_OCCLUDED for that segment under
+ * the same flags; bits >= nset are 0.  trt_point_segments emits the records exactly as the kernel
+ * forms them, so   mask bit == trt_occluded(trt_point_segments(...))[i * nset + k].
+ * In TARGETS mode a segment that is not a valid trt_qseg is not traced and reads 0: a point
+ * coincident with a target, or farther from it than the direction length range allows, sees the
+ * target (host and device arrays alike).
+ *
+ * Read from p: flags only; FLOOR, SPHERES, BATCH_WALK, DEVICE_PTRS and TIMING as by trt_occluded,
+ * TRT_FLAG_COUNT is TRT_ERR_INVALID, everything else is ignored.  With TRT_FLAG_DEVICE_PTRS `pts`
+ * and `out_masks` are device pointers (`set` stays a host array).
+ *
+ * A valid point: pos and n finite, 0 < tmax <= TRT_QSEG_MAX_T, in both modes.  A valid set entry:
+ * a valid ray direction (trt_qray's length range) for DIRS, finite for TARGETS.  The set is always
+ * checked on the host (TRT_ERR_INVALID, the entry's index in trt_last_error).  Host points are
+ * checked before anything runs: a bad one returns TRT_ERR_INVALID with the lowest bad index in
+ * trt_last_error and out_masks untouched.  In a device array a bad point reads TRT_VIS_BAD_POINT
+ * and traces nothing; the other points, those that share its wave included, are unaffected (with
+ * nset <= 63 a mask never equals the marker).
+ *
+ * Sizes, stream and buffers as trt_occluded: npts == 0 is TRT_OK and launches nothing; npts * nset >
+ * TRT_QRAY_MAX_RAYS, nset of 0 or above TRT_VIS_MAX_SET, an unknown mode, or a NULL pts, set or
+ * out_masks with npts > 0 is TRT_ERR_INVALID; a call before trt_upload_scene is TRT_ERR_NOSCENE.
+ * Device `pts` must be 16-byte aligned and device `out_masks` 8-byte aligned.  A device-pointer call
+ * without TIMING only enqueues on the context's stream; host arrays stage through context-owned
+ * buffers that only grow.  The call changes nothing a later frame or query depends on. */
+typedef struct trt_qpoint { float pos[3]; float tmax; float n[3]; float pad; } trt_qpoint; /* 32 B */
+#define TRT_VIS_DIRS 0u
+#define TRT_VIS_TARGETS 1u
+#define TRT_VIS_MAX_SET 63u
+#define TRT_VIS_BAD_POINT 0xffffffffffffffffull
+#ifdef __cplusplus
+static_assert(sizeof(trt_qpoint) == 32, "point records are 32 B");
+#else
+_Static_assert(sizeof(trt_qpoint) == 32, "point records are 32 B");
+#endif
+
+int trt_visibility(trt_ctx* ctx, const trt_params* p, const trt_qpoint* pts, uint32_t npts,
+                   const float* set, uint32_t nset, uint32_t mode, uint64_t* out_masks, trt_stats* st);
+/* host only, no context: TRT_OK when every point is valid, else TRT_ERR_INVALID with the lowest bad
+ * index in *first_bad (may be NULL).  pts NULL with n > 0 is TRT_ERR_INVALID (*first_bad = 0). */
+int trt_check_points(const trt_qpoint* pts, uint32_t n, uint32_t* first_bad);
+/* host only, no context: the npts * nset segments of a visibility query, out[i * nset + k] = segment
+ * (i, k) exactly as the kernel forms it (pad 0).  A degenerate TARGETS segment is emitted as
+ * computed and fails trt_check_segs.  TRT_ERR_INVALID for a bad point or set entry, an nset outside
+ * 1..TRT_VIS_MAX_SET, an unknown mode or a null array. */
+int trt_point_segments(const trt_qpoint* pts, uint32_t npts, const float* set, uint32_t nset,
+                       uint32_t mode, trt_qseg* out /* npts * nset, out[i * nset + k] */);
+
 /* Device time per frame (ms) of each launch timed by the last timed trt_render_frames call:
  * the launch's event span divided by the frames it traced (waits for them); n <= the number
  * of timed launches, trt_timed_launches(). */

@@ -86,6 +86,9 @@ def lib() -> ctypes.CDLL:
         "trt_pixel_ray": (c_int, [ctypes.POINTER(Params), vp, f3, c_u32, c_u32, vp]),
         "trt_occluded": (c_int, [vp, ctypes.POINTER(Params), vp, c_u32, vp, ctypes.POINTER(Stats)]),
         "trt_check_segs": (c_int, [vp, c_u32, ctypes.POINTER(c_u32)]),
+        "trt_visibility": (c_int, [vp, ctypes.POINTER(Params), vp, c_u32, vp, c_u32, c_u32, vp, ctypes.POINTER(Stats)]),
+        "trt_check_points": (c_int, [vp, c_u32, ctypes.POINTER(c_u32)]),
+        "trt_point_segments": (c_int, [vp, c_u32, vp, c_u32, c_u32, vp]),
         "trt_frame_times": (c_int, [vp, ctypes.POINTER(ctypes.c_float), c_u32]),
         "trt_timed_launches": (c_u32, [vp, ctypes.POINTER(c_u32), c_u32]),
         "trt_set_frame_batch": (c_int, [vp, c_u32]),
@@ -176,6 +179,9 @@ ABI_SYMBOLS = (
     "trt_pixel_ray",
     "trt_occluded",
     "trt_check_segs",
+    "trt_visibility",
+    "trt_check_points",
+    "trt_point_segments",
     "trt_frame_times",
     "trt_timed_launches",
     "trt_set_frame_batch",

@@ -101,6 +101,13 @@ struct trt_ctx {
     size_t capqrays = 0;
     void* d_qhits = nullptr;
     size_t capqhits = 0;
+    // trt_visibility: the call's direction or target set (64 x 16 B), copied stream-ordered per
+    // call; its host points stage through d_qrays and its masks through d_out8
+    void* d_visset = nullptr;
+    size_t capvisset = 0;
+    // whether visibility_query_kernel<3> may take the wave-cooperative shadow walk (TRT_VIS_COOP
+    // env): off, every lane walks alone — the faster of the two on hemisphere sets
+    bool vis_coop = false;
     unsigned long long* d_counters = nullptr;
     uint32_t num_cus = 256;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;

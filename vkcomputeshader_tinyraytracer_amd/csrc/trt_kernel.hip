@@ -34,6 +34,7 @@
 #include "trt_bands.h"
 #include "trt_device.h"
 #include "trt_math.h"
+#include "trt_qpoint.h"
 #include "trt_qray.h"
 
 namespace trt {
@@ -1066,7 +1067,9 @@ __device__ __forceinline__ void scene_intersect(const KArgs& A, f3 o, f3 d, Hit&
 // returns false).  A query whose four bits are clear in every lane is done after one ballot (most
 // floor tiles); otherwise a sphere whose bit is clear in every lane still in the query is not
 // tested: one ballot and a scalar branch around sphere_hit, nothing per lane.
-template <bool COUNT, int GEOM, bool SMASK = false>
+// COOP = false (visibility_query_kernel's per-lane instantiation only) never takes the
+// wave-cooperative walk below; every other caller leaves the gate as it is.
+template <bool COUNT, int GEOM, bool SMASK = false, bool COOP = true>
 __device__ __forceinline__ bool shadow_intersect(const KArgs& A, f3 o, f3 d, float max_dist, Cnt& c,
                                                  float4* slab, uint32_t sm = 0xFu) {
     static_assert(!SMASK || (GEOM == 0 && !COUNT), "the occluder masks serve plain GEOM 0 frames");
@@ -1105,7 +1108,7 @@ __device__ __forceinline__ bool shadow_intersect(const KArgs& A, f3 o, f3 d, flo
     Hit unused;
     if (GEOM >= 2) {
 #if TRT_SHADOW_WAVE && TRT_BVH_QUANT
-        if constexpr (!COUNT && GEOM == 3 && TRT_BVH_WIDTH == 4 && slab_words<GEOM>() >= kShadowWaveStack)
+        if constexpr (COOP && !COUNT && GEOM == 3 && TRT_BVH_WIDTH == 4 && slab_words<GEOM>() >= kShadowWaveStack)
             if (A.bvh4q) {
                 // only when the walking lanes' origins lie within TRT_SHADOW_WAVE_EXT of the
                 // first one's (L-inf): scattered origins make the union of the walks far longer
@@ -3331,6 +3334,85 @@ hipError_t launch_occlusion_query(const KArgs& A0, const float4* segs, uint32_t 
     const dim3 grid((n + 63u) / 64u), block(64);
     dispatch_geom(geom_of(A), [&](auto g) {
         hipLaunchKernelGGL(occlusion_query_kernel<decltype(g)::value>, grid, block, 0, stream, A, segs, n, out);
+    });
+    return hipGetLastError();
+}
+#endif
+
+// Visibility masks (abi.h trt_visibility): the gather form of the occlusion query.  Every point
+// asks the same nset <= 63 questions (a direction or target set shared by all points, in a small
+// device buffer); the segments are formed here (trt_qpoint.h, the arithmetic trt_point_segments
+// restates on the host) and one 64-bit mask per point comes out.  A point takes L = 2^lg lanes, the
+// smallest power of two >= nset, so a one-wave workgroup holds 64 / L consecutive points: lane l
+// serves point (64 / L) * block + l / L, entry l % L, and is idle when l % L >= nset or the point
+// is past npts.  Each live lane loads its point (two 16-byte loads; the L lanes of a point read the
+// same 32 bytes) and its entry, applies the point predicate, forms the segment and then does
+// exactly what occlusion_query_kernel does with a record: normalize3, the floor test,
+// shadow_intersect<false, GEOM>.  Idle lanes, the lanes of a bad point and those of a TARGETS
+// segment that is no valid segment never enter the walk (shadow_intersect takes any subset of a
+// wave, see occlusion_query_kernel).  One ballot of the verdicts is the answer: the lane with
+// entry 0 of each point shifts its point's L-bit slice down and does one 8-byte store — lanes that
+// did not walk voted 0, so bits >= nset are clear — or stores the marker for a bad point.  With L =
+// 64 every walking lane shares one origin, so a quantized-BVH scene takes shadow_wave_q by
+// shadow_intersect's own gate; with a smaller L the gate decides as it does for any wave.
+// COOP = false (GEOM 3 only: a second instantiation, shadow_intersect<false, 3, false, false>) never
+// takes shadow_wave_q: the directions of a hemisphere diverge, and the union of their walks is then
+// longer than each lane's own walk (measured: DESIGN.md §5; the context chooses, TRT_VIS_COOP).
+template <int GEOM, bool COOP>
+__global__ __launch_bounds__(64, waves_per_simd<GEOM>()) void visibility_query_kernel(
+    KArgs A, const float4* __restrict__ pts, uint32_t npts, const float4* __restrict__ set, uint32_t nset, uint32_t lg,
+    uint32_t mode, uint64_t* __restrict__ out) {
+    __shared__ float4 slab[slab_float4s<GEOM>()];
+    const uint32_t lane = threadIdx.x;
+    const uint32_t k = lane & ((1u << lg) - 1u);
+    const uint32_t i = (blockIdx.x << (6u - lg)) + (lane >> lg);
+    const bool live = k < nset && i < npts;
+    bool bad = false, occ = false;
+    if (live) {
+        const float4 a = pts[2 * (size_t)i], b = pts[2 * (size_t)i + 1];
+        const float4 e = set[k];
+        bad = !qpoint_valid(a.x, a.y, a.z, a.w, b.x, b.y, b.z);
+        if (!bad) {
+            const QPointSeg s = qpoint_segment(mode, a.x, a.y, a.z, a.w, b.x, b.y, b.z, e.x, e.y, e.z);
+            if (qseg_valid(a.x, a.y, a.z, s.dx, s.dy, s.dz, s.tmax)) {
+                const f3 o = mk(a.x, a.y, a.z);
+                const f3 d = normalize3(mk(s.dx, s.dy, s.dz)); // shader.comp:593
+                if (A.flags & TRT_FLAG_FLOOR) { // as occlusion_query_kernel
+                    float tfloor;
+                    occ = floor_hit(o, d, s.tmax, tfloor);
+                }
+                if (!occ) {
+                    Cnt cnt;
+                    occ = shadow_intersect<false, GEOM, false, COOP>(A, o, d, s.tmax, cnt, slab);
+                }
+            }
+        }
+    }
+    const uint64_t verdicts = __ballot(occ);
+    if (live && k == 0u) {
+        const uint64_t mine = (verdicts >> lane) & (~0ull >> (64u - (1u << lg)));
+        out[i] = bad ? (uint64_t)TRT_VIS_BAD_POINT : mine;
+    }
+}
+
+#ifndef TRT_KRES_ONLY
+hipError_t launch_visibility_query(const KArgs& A0, const float4* pts, uint32_t npts, const float4* set, uint32_t nset,
+                                   uint32_t mode, bool coop, uint64_t* out, hipStream_t stream) {
+    if (!npts) return hipSuccess;
+    if (nset < 1u || nset > TRT_VIS_MAX_SET) return hipErrorInvalidValue;
+    KArgs A = A0;
+    A.diag = nullptr;
+    uint32_t lg = 0; // lanes per point: the smallest power of two >= nset
+    while ((1u << lg) < nset) ++lg;
+    const uint32_t per_wave = 64u >> lg;
+    const dim3 grid((npts + per_wave - 1u) / per_wave), block(64);
+    dispatch_geom(geom_of(A), [&](auto g) {
+        constexpr int G = decltype(g)::value;
+        // the cooperative walk exists for GEOM 3 alone: the other geometries have the one kernel
+        if (G == 3 && !coop)
+            hipLaunchKernelGGL((visibility_query_kernel<G, G != 3>), grid, block, 0, stream, A, pts, npts, set, nset, lg, mode, out);
+        else
+            hipLaunchKernelGGL((visibility_query_kernel<G, true>), grid, block, 0, stream, A, pts, npts, set, nset, lg, mode, out);
     });
     return hipGetLastError();
 }

@@ -20,6 +20,7 @@
 #include "scene_pack.h"
 #include "trt_bands.h"
 #include "trt_internal.h"
+#include "trt_qpoint.h"
 #include "trt_qray.h"
 
 namespace trt {
@@ -138,10 +139,25 @@ int first_invalid(const R* recs, uint32_t n, uint32_t* first_bad, Valid valid) {
     return TRT_OK;
 }
 
+// The direction or target set of a visibility query (trt_visibility, trt_point_segments): a known
+// mode, 1..TRT_VIS_MAX_SET entries, each valid for the mode.  *bad (may be null): the first entry
+// that fails, or nset when the mode, the count or a null array is at fault.
+int check_vis_set(const float* set, uint32_t nset, uint32_t mode, uint32_t* bad) {
+    if (bad) *bad = nset;
+    if ((mode != TRT_VIS_DIRS && mode != TRT_VIS_TARGETS) || nset < 1u || nset > TRT_VIS_MAX_SET || !set) return TRT_ERR_INVALID;
+    for (uint32_t k = 0; k < nset; ++k) {
+        if (trt::qset_entry_valid(mode, set[4 * k], set[4 * k + 1], set[4 * k + 2])) continue;
+        if (bad) *bad = k;
+        return TRT_ERR_INVALID;
+    }
+    return TRT_OK;
+}
+
 // A new context's knobs; the per-call ones, which tests change between calls, are read per call.
 void read_env_knobs(trt_ctx* c) {
     if (const char* e = std::getenv("TRT_BVH_WAVES4")) c->bvh_waves4 = std::atoi(e) != 0 ? 1 : 0;
     if (const char* e = std::getenv("TRT_SPP_LANES")) c->spp_lanes = std::atoi(e) != 0;
+    if (const char* e = std::getenv("TRT_VIS_COOP")) c->vis_coop = std::atoi(e) != 0;
     if (const char* e = std::getenv("TRT_DEFER_PPW")) { // pass-A pixels per wave: 64, 32, 16 or 8
         const int ppw = std::atoi(e);
         c->defer_sub = ppw == 8 ? 8u : ppw == 16 ? 4u : ppw == 32 ? 2u : ppw == 64 ? 1u : 0u;
@@ -247,6 +263,27 @@ int trt_check_segs(const trt_qseg* segs, uint32_t n, uint32_t* first_bad) {
     });
 }
 
+int trt_check_points(const trt_qpoint* pts, uint32_t n, uint32_t* first_bad) {
+    return first_invalid(pts, n, first_bad, [](const trt_qpoint& q) {
+        return trt::qpoint_valid(q.pos[0], q.pos[1], q.pos[2], q.tmax, q.n[0], q.n[1], q.n[2]);
+    });
+}
+
+int trt_point_segments(const trt_qpoint* pts, uint32_t npts, const float* set, uint32_t nset, uint32_t mode, trt_qseg* out) {
+    if (check_vis_set(set, nset, mode, nullptr) != TRT_OK) return TRT_ERR_INVALID;
+    if (trt_check_points(pts, npts, nullptr) != TRT_OK || (npts && !out)) return TRT_ERR_INVALID;
+    for (uint32_t i = 0; i < npts; ++i) {
+        const trt_qpoint& q = pts[i];
+        for (uint32_t k = 0; k < nset; ++k) {
+            const float* e = set + 4 * (size_t)k;
+            const trt::QPointSeg s =
+                trt::qpoint_segment(mode, q.pos[0], q.pos[1], q.pos[2], q.tmax, q.n[0], q.n[1], q.n[2], e[0], e[1], e[2]);
+            out[(size_t)i * nset + k] = trt_qseg{{q.pos[0], q.pos[1], q.pos[2]}, s.tmax, {s.dx, s.dy, s.dz}, 0.0f};
+        }
+    }
+    return TRT_OK;
+}
+
 void trt_params_default(trt_params* p) {
     if (!p) return;
     std::memset(p, 0, sizeof(*p));
@@ -307,7 +344,7 @@ int trt_destroy(trt_ctx* c) {
     (void)hipDeviceSynchronize();
     free_scene(c);
     for (void* p : {(void*)c->d_envp, (void*)c->d_sky, (void*)c->d_smask, c->d_out8, c->d_out32, c->d_rays, c->d_qrays,
-                    c->d_qhits, (void*)c->d_counters})
+                    c->d_qhits, c->d_visset, (void*)c->d_counters})
         (void)hipFree(p);
     for (hipEvent_t e : c->fev) (void)hipEventDestroy(e);
     for (auto& b : c->split) {
@@ -1457,6 +1494,73 @@ int trt_occluded(trt_ctx* c, const trt_params* p, const trt_qseg* segs, uint32_t
     if ((rc = begin_call(c, false, timing)) != TRT_OK) return rc;
     HIP_TRY(c, trt::launch_occlusion_query(A, d_segs, nsegs, d_out, c->stream));
     return finish_call(c, dev, false, timing, st, {{out, d_out, n}});
+}
+
+// Visibility masks (abi.h): the gather form of trt_occluded through visibility_query_kernel, which
+// forms the npts * nset segments itself.  The set, always a host array, is checked here and copied
+// stream-ordered into a small buffer of the context; host points stage through the ray-query record
+// buffer and the masks through the RGBA8 buffer (hipMalloc's alignment serves both).  Like
+// trt_occluded it writes nothing of the context that a frame or a query depends on.
+int trt_visibility(trt_ctx* c, const trt_params* p, const trt_qpoint* pts, uint32_t npts, const float* set, uint32_t nset,
+                   uint32_t mode, uint64_t* out, trt_stats* st) {
+    if (!c) return TRT_ERR_INVALID;
+    if (!p) return fail(c, TRT_ERR_INVALID, "trt_visibility: null params");
+    if (!c->have_scene) return fail(c, TRT_ERR_NOSCENE, "trt_visibility: no scene uploaded");
+    if (p->flags & TRT_FLAG_COUNT)
+        return fail(c, TRT_ERR_INVALID, "trt_visibility: TRT_FLAG_COUNT is not offered (any-hit counters depend on the walk order)");
+    if ((p->flags & TRT_FLAG_TIMING) && !st) return fail(c, TRT_ERR_INVALID, "trt_visibility: TRT_FLAG_TIMING needs stats");
+    if (mode != TRT_VIS_DIRS && mode != TRT_VIS_TARGETS) return fail(c, TRT_ERR_INVALID, "trt_visibility: unknown mode");
+    if (nset < 1u || nset > TRT_VIS_MAX_SET) return fail(c, TRT_ERR_INVALID, "trt_visibility: a set holds 1..63 entries");
+    if ((uint64_t)npts * nset > TRT_QRAY_MAX_RAYS) return fail(c, TRT_ERR_INVALID, "trt_visibility: more than 2^28 segments");
+    if (npts && !pts) return fail(c, TRT_ERR_INVALID, "trt_visibility: null pts");
+    if (npts && !set) return fail(c, TRT_ERR_INVALID, "trt_visibility: null set");
+    if (npts && !out) return fail(c, TRT_ERR_INVALID, "trt_visibility: null out_masks");
+    const bool dev = (p->flags & TRT_FLAG_DEVICE_PTRS) != 0;
+    // the kernel reads a point as two 16-byte vectors straight from the caller's device array and
+    // stores whole 8-byte masks (host arrays are staged)
+    if (dev && (reinterpret_cast<uintptr_t>(pts) & 15u))
+        return fail(c, TRT_ERR_INVALID, "trt_visibility: device pts must be 16-byte aligned");
+    if (dev && (reinterpret_cast<uintptr_t>(out) & 7u))
+        return fail(c, TRT_ERR_INVALID, "trt_visibility: device out_masks must be 8-byte aligned");
+    if (set) {
+        uint32_t bad = 0;
+        if (check_vis_set(set, nset, mode, &bad) != TRT_OK)
+            return fail(c, TRT_ERR_INVALID, "trt_visibility: set entry " + std::to_string(bad) +
+                                                (mode == TRT_VIS_DIRS ? " is not a valid direction (non-finite, or length out of range)"
+                                                                      : " is not finite"));
+    }
+    const bool timing = (p->flags & TRT_FLAG_TIMING) != 0;
+    if (st) std::memset(st, 0, sizeof(*st));
+    if (npts == 0) return TRT_OK;
+    if (!dev) { // a device array cannot be read here: the kernel applies the same predicate
+        uint32_t bad = 0;
+        if (trt_check_points(pts, npts, &bad) != TRT_OK)
+            return fail(c, TRT_ERR_INVALID, "trt_visibility: point " + std::to_string(bad) +
+                                                " is not valid (non-finite pos or n, or tmax out of range)");
+    }
+    HIP_TRY(c, hipSetDevice(c->device));
+
+    const trt_params q = query_params(p, 1, TRT_FLAG_SPHERES | TRT_FLAG_FLOOR | TRT_FLAG_BATCH_WALK | TRT_FLAG_DEVICE_PTRS | TRT_FLAG_TIMING);
+    int rc;
+    KArgs A;
+    fill_args(c, &q, A);
+    A.view_on = 0;
+
+    const float4* d_pts = reinterpret_cast<const float4*>(pts);
+    uint64_t* d_out = out;
+    const size_t n = npts;
+    // the buffer holds a whole 64-entry set whatever nset is; the copy is ordered on the stream
+    // behind an earlier query's kernel, which may still be reading the buffer
+    if ((rc = ensure(c, &c->d_visset, &c->capvisset, 64 * 4 * sizeof(float), "alloc visibility set")) != TRT_OK) return rc;
+    HIP_TRY(c, hipMemcpyAsync(c->d_visset, set, (size_t)nset * 4 * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    const float4* d_set = static_cast<const float4*>(c->d_visset);
+    if (!dev) {
+        if ((rc = stage(c, &c->d_qrays, &c->capqrays, n * sizeof(trt_qpoint), "alloc query points", pts, &d_pts)) != TRT_OK) return rc;
+        if ((rc = stage(c, &c->d_out8, &c->cap8, n * sizeof(uint64_t), "alloc visibility masks", nullptr, &d_out)) != TRT_OK) return rc;
+    }
+    if ((rc = begin_call(c, false, timing)) != TRT_OK) return rc;
+    HIP_TRY(c, trt::launch_visibility_query(A, d_pts, npts, d_set, nset, mode, c->vis_coop, d_out, c->stream));
+    return finish_call(c, dev, false, timing, st, {{out, d_out, n * sizeof(uint64_t)}});
 }
 
 } // extern "C"

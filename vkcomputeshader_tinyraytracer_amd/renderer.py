@@ -302,6 +302,62 @@ class Renderer:
         self._check(self._L.trt_occluded(self._h, ctypes.byref(p), ptrs[0], n, ptrs[1], ctypes.byref(st)))
         return (out, st.as_dict()) if timing else out
 
+    # -- visibility masks --------------------------------------------------------------------
+    def visibility(self, points, params: T.Params, *, dirs=None, targets=None, out=None, timing: bool = False,
+                   npoints: int | None = None):
+        """The gather form of `occluded` (trt_visibility): every point asks the same K <=
+        T.VIS_MAX_SET questions and gets one 64-bit mask back, bit k set = occluded.  Exactly one of
+        `dirs` (directions, each turned into the hemisphere of the point's n; tmax cuts them off)
+        and `targets` (points such as the lights; tmax caps the range) is a (K, 3) or (K, 4) host
+        array.  The segments are made in the kernel: bit k of mask i is
+        occluded(scene.point_segments(points, ...)[i, k]).  `points` is a numpy array of T.QPOINT
+        (host, synchronous, every point validated first: a bad one raises TrtError and leaves `out`
+        untouched) and gives a (n,) uint64 array, or a contiguous torch CUDA tensor holding such
+        records (16-byte aligned, only enqueued on the context's stream unless timing) and gives a
+        torch.int64 tensor in which a point that is not valid reads -1 (T.VIS_BAD_POINT).  Flags
+        of `params` as for `occluded`; `out` may be longer than the query; `npoints` limits the
+        query to the first points.
+        Returns the masks, or with `timing` the pair (masks, stats_dict)."""
+        from .scene import visibility_set
+
+        mode, e = visibility_set(dirs, targets)
+        p = T.Params.from_buffer_copy(params)
+        p.rays_in = None
+        if _is_torch_cuda(points):
+            import torch
+
+            if not points.is_contiguous():
+                raise ValueError("points must be a contiguous device tensor of T.QPOINT records")
+            have = points.numel() * points.element_size() // T.QPOINT.itemsize
+            n = have if npoints is None else int(npoints)
+            if n > have:
+                raise ValueError(f"{n} points asked of a tensor that holds {have}")
+            p.flags |= T.FLAG_DEVICE_PTRS
+            if out is None:
+                out = torch.empty((n,), dtype=torch.int64, device=points.device)
+            if not (_is_torch_cuda(out) and out.is_contiguous() and out.numel() * out.element_size() >= n * 8):
+                raise ValueError("the output of a device query is a contiguous device tensor that holds every mask")
+            ptrs = (points.data_ptr(), out.data_ptr())
+        else:
+            p.flags &= ~T.FLAG_DEVICE_PTRS
+            s = None if points is None else np.ascontiguousarray(points, T.QPOINT).reshape(-1)
+            n = (0 if s is None else s.shape[0]) if npoints is None else int(npoints)
+            if s is not None and n > s.shape[0]:
+                raise ValueError(f"{n} points asked of an array that holds {s.shape[0]}")
+            if out is None:
+                out = np.empty((n,), np.uint64)
+            if not (isinstance(out, np.ndarray) and out.flags["C_CONTIGUOUS"] and out.dtype == np.uint64 and out.size >= n):
+                raise ValueError("the output of a host query is a C-contiguous uint64 numpy array that holds every mask")
+            ptrs = (None if s is None or not len(s) else s.ctypes.data, out.ctypes.data)
+        if timing:
+            p.flags |= T.FLAG_TIMING
+        else:
+            p.flags &= ~T.FLAG_TIMING
+        st = T.Stats()
+        self._check(self._L.trt_visibility(self._h, ctypes.byref(p), ptrs[0], n, e.ctypes.data if len(e) else None,
+                                           len(e), mode, ptrs[1], ctypes.byref(st)))
+        return (out, st.as_dict()) if timing else out
+
     def pixel_ray(self, params: T.Params, x: int, y: int) -> np.ndarray:
         """The T.QRAY of pixel (x, y)'s primary ray at spp 1 under the context's current UBO
         (camPos) and view (trt_pixel_ray)."""

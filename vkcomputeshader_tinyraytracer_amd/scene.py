@@ -217,6 +217,72 @@ def segments_from_rays(qrays, tmax=T.QSEG_MAX_T) -> np.ndarray:
     return s
 
 
+def sphere_dirs(k: int) -> np.ndarray:
+    """`k` unit directions spread evenly over the sphere (a Fibonacci spiral about the y axis, from
+    near +y to near -y), (k, 3) float32, computed in float64 and rounded once.  With
+    Renderer.visibility(..., dirs=) each is turned into the hemisphere of a point's normal, so k
+    directions sample that hemisphere k times (ambient occlusion = popcount(mask) / k)."""
+    if k < 1:
+        raise ValueError("at least one direction")
+    i = np.arange(k, dtype=np.float64)
+    y = 1.0 - (2.0 * i + 1.0) / k
+    r = np.sqrt(1.0 - y * y)
+    phi = i * (np.pi * (3.0 - np.sqrt(5.0)))  # the golden angle
+    d = np.stack([r * np.cos(phi), y, r * np.sin(phi)], 1)
+    d /= np.sqrt((d * d).sum(1))[:, None]
+    return d.astype(np.float32)
+
+
+def points_on_hits(rays, hits, offset: float = 1e-3, tmax=T.QSEG_MAX_T) -> tuple[np.ndarray, np.ndarray]:
+    """One T.QPOINT per ray that hit something (Renderer.trace_rays' T.QHIT records): the hit point
+    org + t normalize(dir), moved `offset` along the record's normal turned against the ray, with
+    that turned normal as the point's n — the place a shader's secondary rays start from.
+    Computed in float64 and rounded once.  Returns (points, the ray index of each point)."""
+    r = np.asarray(rays, T.QRAY).reshape(-1)
+    h = np.asarray(hits, T.QHIT).reshape(-1)
+    if len(r) != len(h):
+        raise ValueError("one hit record per ray")
+    idx = np.flatnonzero((h["kind"] != T.HIT_NONE) & (h["kind"] != T.HIT_BAD_RAY))
+    o = r["org"][idx].astype(np.float64)
+    d = r["dir"][idx].astype(np.float64)
+    d /= np.sqrt((d * d).sum(1))[:, None]
+    n = h["n"][idx].astype(np.float64)
+    n = np.where(((n * d).sum(1) > 0.0)[:, None], -n, n)
+    pts = np.zeros(len(idx), T.QPOINT)
+    pts["pos"] = o + h["t"][idx].astype(np.float64)[:, None] * d + float(offset) * n
+    pts["n"] = n
+    pts["tmax"] = np.asarray(tmax, np.float32)
+    return pts, idx
+
+
+def visibility_set(dirs=None, targets=None) -> tuple[int, np.ndarray]:
+    """(mode, the (K, 4) float32 set array of trt_visibility) from exactly one of `dirs` /
+    `targets`, (K, 3) or (K, 4) arrays (a fourth column is carried and ignored)."""
+    if (dirs is None) == (targets is None):
+        raise ValueError("exactly one of dirs= and targets=")
+    a = np.asarray(dirs if targets is None else targets, np.float32)
+    if a.ndim != 2 or a.shape[1] not in (3, 4):
+        raise ValueError("a direction or target set is a (K, 3) or (K, 4) array")
+    e = np.zeros((a.shape[0], 4), np.float32)
+    e[:, : a.shape[1]] = a
+    return (T.VIS_DIRS if targets is None else T.VIS_TARGETS), e
+
+
+def point_segments(points, dirs=None, targets=None) -> np.ndarray:
+    """The (npoints, K) T.QSEG records Renderer.visibility traces for `points` (T.QPOINT) and a
+    direction or target set, exactly as the kernel forms them (trt_point_segments):
+    visibility bit k of point i == Renderer.occluded of record [i, k].  A target record that is
+    not a valid segment (a point on its target) is returned as computed; its bit reads 0."""
+    mode, e = visibility_set(dirs, targets)
+    p = np.ascontiguousarray(points, T.QPOINT).reshape(-1)
+    out = np.zeros((len(p), len(e)), T.QSEG)
+    rc = lib().trt_point_segments(p.ctypes.data if len(p) else None, len(p), e.ctypes.data if len(e) else None, len(e),
+                                  mode, out.ctypes.data if out.size else None)
+    if rc != 0:
+        raise TrtError(rc, "trt_point_segments: a point or set entry is not valid, or the set does not hold 1..63 entries")
+    return out
+
+
 def camera_orbit(ubo: np.ndarray, n: int, speed: float = 0.02, yaw_step: float = 1.0, pitch_step: float = -0.25,
                  yaw0: float = 0.0, pitch0: float = 0.0) -> tuple[np.ndarray, np.ndarray]:
     """camera_path with a camera that turns while it walks (mouse look held with W and D): n

@@ -65,6 +65,14 @@ OCC_OCCLUDED = 1
 OCC_BAD_SEG = 0xFF  # a device-pointer query's byte for a segment that is not valid
 QSEG_MAX_T = np.float32(1e10)  # TRT_QSEG_MAX_T: the shader's initial nearest distance, "a whole ray"
 assert QSEG.itemsize == 32
+# abi.h trt_qpoint: a point of a visibility query (Renderer.visibility); n only chooses the side
+# of a TRT_VIS_DIRS direction, tmax cuts a direction off and caps the range to a target
+QPOINT = np.dtype([("pos", "<f4", (3,)), ("tmax", "<f4"), ("n", "<f4", (3,)), ("pad", "<f4")])
+VIS_DIRS = 0  # set entries are directions, turned into the hemisphere of n
+VIS_TARGETS = 1  # set entries are points (lights): segments from each point to each target
+VIS_MAX_SET = 63
+VIS_BAD_POINT = 0xFFFFFFFFFFFFFFFF  # a device-pointer query's mask of a point that is not valid (-1 as int64)
+assert QPOINT.itemsize == 32
 
 assert VIEW.itemsize == 36 and QRAY.itemsize == 32 and QHIT.itemsize == 32
 assert MATERIAL.itemsize == 48 and SPHERE.itemsize == 64
