@@ -478,6 +478,55 @@ int trt_check_points(const trt_qpoint* pts, uint32_t n, uint32_t* first_bad);
 int trt_point_segments(const trt_qpoint* pts, uint32_t npts, const float* set, uint32_t nset,
                        uint32_t mode, trt_qseg* out /* npts * nset, out[i * nset + k] */);
 
+/* ---- all-hits queries: every surface crossing of a segment, in order ---------------------------
+ * trt_trace_rays reports the first surface of a ray and trt_occluded whether a segment meets any;
+ * trt_trace_all reports EVERYTHING a segment crosses, nearest first, and how many crossings there
+ * are: thickness along a ray, absorption, X-ray views, inside / outside by parity.
+ *
+ * Segment i is a trt_qseg exactly as trt_occluded reads it: org, d = normalize(dir) by the shader's
+ * own normalize, cut off at tmax; the same valid-record predicate.
+ *
+ * Its hits are the shader's own primitive tests, each kept iff MIN_EPSILON < t < tmax (both strict):
+ *   floor     with TRT_FLAG_FLOOR, scene_intersect's floor test: at most one hit;
+ *   sphere i  with TRT_FLAG_SPHERES, both roots of ray_sphere_intersect's terms, t0 = tca - thc then
+ *             t1 = tca + thc, each if > MIN_EPSILON; t1 is dropped when it equals a kept t0 (a
+ *             tangent ray gives one hit).  The first root reported is the t trt_trace_rays reports;
+ *   triangle  one candidate per (batch, triangle) pair of the reference's loop: the batch passes
+ *             ray_aabb_intersect and Moller-Trumbore passes, exactly as a nearest-hit query tests.
+ *             A triangle the BVH references twice (a spatial split) is still one candidate.
+ * They are ordered by the key (t, class, a, b): class 0 the floor, 1 a sphere (a = its index), 2 a
+ * triangle (a = batch index, b = the caller's triangle index): the order in which scene_intersect
+ * resolves ties (floor before sphere before triangle at equal t, lower sphere index first, then
+ * (batch, triangle)).
+ *
+ * hits[i * max_hits + j] is the j-th hit in that order, a trt_qhit with the field meanings of
+ * trt_trace_rays (n before any facing flip; u, v for triangles).  With m = min(total, max_hits),
+ * slots j >= m receive the miss record (t = 1e10, TRT_HIT_NONE, zeros), and
+ *   counts[i] = m | (TRT_ALLHITS_MORE if an (m + 1)-th hit exists inside tmax).
+ * hits may be NULL: only the counts are produced, and max_hits still bounds them.
+ * For every valid segment: (counts[i] & 0x7fffffff) > 0 equals trt_occluded's byte; record 0 equals
+ * the trt_trace_rays record of the same ray, bit for bit, whenever that record's t < tmax; and the
+ * answer for max_hits = K is the first K records of the answer for any larger value.
+ *
+ * Read from p: flags only; FLOOR, SPHERES, BATCH_WALK, DEVICE_PTRS and TIMING as by trt_occluded,
+ * TRT_FLAG_COUNT is TRT_ERR_INVALID, everything else is ignored.  max_hits outside
+ * 1..TRT_ALLHITS_MAX, nsegs * max_hits > TRT_QRAY_MAX_RAYS, or a NULL segs or counts with nsegs > 0
+ * is TRT_ERR_INVALID; nsegs == 0 is TRT_OK and launches nothing; a call before trt_upload_scene is
+ * TRT_ERR_NOSCENE.  Host arrays are validated first: a bad record returns TRT_ERR_INVALID with the
+ * lowest bad index in trt_last_error and the outputs untouched; they then stage through
+ * context-owned buffers that only grow.  In a device array a bad record traces nothing: its count
+ * reads TRT_ALLHITS_BAD_SEG and every one of its slots kind TRT_HIT_BAD_RAY with zeros elsewhere;
+ * the other segments of its wave are unaffected.  Device `segs` and `hits` must be 16-byte aligned
+ * and `counts` 4-byte aligned.  A device-pointer call without TIMING only enqueues on the
+ * context's stream.  The cost is one nearest-hit walk per reported hit plus one (the searches
+ * restart from the root).  The call changes nothing a later frame or query depends on. */
+#define TRT_ALLHITS_MAX 32u              /* max_hits in 1..32 */
+#define TRT_ALLHITS_MORE 0x80000000u     /* in counts[i]: further hits exist inside tmax */
+#define TRT_ALLHITS_BAD_SEG 0xffffffffu  /* counts[i] of a bad record in a device array */
+int trt_trace_all(trt_ctx* ctx, const trt_params* p, const trt_qseg* segs, uint32_t nsegs,
+                  uint32_t max_hits, trt_qhit* hits /* nsegs * max_hits, or NULL */,
+                  uint32_t* counts /* nsegs */, trt_stats* st);
+
 /* Device time per frame (ms) of each launch timed by the last timed trt_render_frames call:
  * the launch's event span divided by the frames it traced (waits for them); n <= the number
  * of timed launches, trt_timed_launches(). */

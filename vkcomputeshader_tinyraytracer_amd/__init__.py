@@ -18,8 +18,10 @@ from .scene import (
     config_c5,
     config_readme,
     config_reference_default,
+    crossing_parity,
     equirect_qrays,
     icosphere,
+    inside_length,
     make_ubo,
     pinhole_qrays,
     point_segments,
@@ -36,5 +38,5 @@ __all__ = [
     "MODEL_INFOS", "Scene", "SceneBuilder", "camera_path", "config_c1", "config_c2", "config_c3", "config_c4",
     "config_c5", "config_readme", "config_reference_default", "icosphere", "make_ubo", "synthetic_envmap", "write_image",
     "camera_orbit", "view_look", "view_rays", "view_ypr", "pinhole_qrays", "equirect_qrays",
-    "point_segments", "points_on_hits", "sphere_dirs",
+    "point_segments", "points_on_hits", "sphere_dirs", "inside_length", "crossing_parity",
 ]

@@ -86,6 +86,7 @@ def lib() -> ctypes.CDLL:
         "trt_pixel_ray": (c_int, [ctypes.POINTER(Params), vp, f3, c_u32, c_u32, vp]),
         "trt_occluded": (c_int, [vp, ctypes.POINTER(Params), vp, c_u32, vp, ctypes.POINTER(Stats)]),
         "trt_check_segs": (c_int, [vp, c_u32, ctypes.POINTER(c_u32)]),
+        "trt_trace_all": (c_int, [vp, ctypes.POINTER(Params), vp, c_u32, c_u32, vp, vp, ctypes.POINTER(Stats)]),
         "trt_visibility": (c_int, [vp, ctypes.POINTER(Params), vp, c_u32, vp, c_u32, c_u32, vp, ctypes.POINTER(Stats)]),
         "trt_check_points": (c_int, [vp, c_u32, ctypes.POINTER(c_u32)]),
         "trt_point_segments": (c_int, [vp, c_u32, vp, c_u32, c_u32, vp]),
@@ -182,6 +183,7 @@ ABI_SYMBOLS = (
     "trt_visibility",
     "trt_check_points",
     "trt_point_segments",
+    "trt_trace_all",
     "trt_frame_times",
     "trt_timed_launches",
     "trt_set_frame_batch",

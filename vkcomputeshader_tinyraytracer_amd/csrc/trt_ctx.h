@@ -96,7 +96,8 @@ struct trt_ctx {
     void* d_rays = nullptr;
     size_t caprays = 0;
     // trt_trace_rays with host pointers: the staged ray and hit records (its colours stage
-    // through d_out8 / d_out32); grow-only like the others
+    // through d_out8 / d_out32); grow-only like the others.  trt_trace_all stages its segments
+    // through d_qrays, its nsegs * max_hits records through d_qhits and its counts through d_out8
     void* d_qrays = nullptr;
     size_t capqrays = 0;
     void* d_qhits = nullptr;

@@ -14,6 +14,8 @@ hipError_t launch_shadow_batch(const KArgs& A, const float4* rays, uint32_t n, u
 hipError_t launch_ray_query(const KArgs& A, const float4* rays, uint32_t n, uint32_t* out8, float4* out32, uint4* hits,
                             bool count, hipStream_t stream);
 hipError_t launch_occlusion_query(const KArgs& A, const float4* segs, uint32_t n, uint8_t* out, hipStream_t stream);
+hipError_t launch_all_hits(const KArgs& A, const float4* segs, uint32_t n, uint32_t max_hits, uint4* hits, uint32_t* counts,
+                           hipStream_t stream);
 hipError_t launch_visibility_query(const KArgs& A, const float4* pts, uint32_t npts, const float4* set, uint32_t nset,
                                    uint32_t mode, bool coop, uint64_t* out, hipStream_t stream);
 namespace jpeg { struct Image; const Image* image_of(const trt_jpeg* j); }

@@ -186,6 +186,37 @@ struct Hit {
     uint32_t batch; // that batch (BVH tie-break on (t, batch, triangle))
 };
 
+// The total order scene_intersect resolves ties in, as a key: (t, class, a, b), class 0 the floor,
+// 1 a sphere (a = its index), 2 a triangle (a = batch, b = the caller's triangle index); `k` packs
+// (class, a, b), a and b below 2^31.  The all-hits query (all_hits_kernel) runs the nearest-hit
+// search with AFTER = true: a candidate then counts only if its key is strictly greater than `lo`,
+// the key of the record found before.  Every other caller leaves AFTER false and passes no key.
+struct HitKey {
+    float t = 0.0f; // below every candidate (t > MIN_EPSILON)
+    uint64_t k = 0;
+};
+__device__ __forceinline__ uint64_t hit_key(uint32_t cls, uint32_t a, uint32_t b) {
+    return ((uint64_t)cls << 62) | ((uint64_t)a << 31) | (uint64_t)b;
+}
+__device__ __forceinline__ bool key_after(const HitKey& lo, float t, uint64_t k) {
+    return t > lo.t || (t == lo.t && k > lo.k);
+}
+// sphere_hit's terms with both roots as candidates: the nearer root beyond MIN_EPSILON whose key
+// (t, k) comes after lo.  With lo below every candidate this is sphere_hit's t.
+__device__ __forceinline__ bool sphere_hit_after(f3 o, f3 d, const SphereArg& s, const HitKey& lo, uint64_t k, float& t) {
+    f3 L = sub(mk(s.c[0], s.c[1], s.c[2]), o);
+    float tca = dot3(L, d);
+    float d2 = dot3(L, L) - tca * tca;
+    float r2 = s.r * s.r;
+    if (d2 > r2) return false;
+    float thc = sqrt_rn(r2 - d2);
+    float t0 = tca - thc, t1 = tca + thc;
+    if (t0 > TRT_EPS && key_after(lo, t0, k)) t = t0;
+    else if (t1 > TRT_EPS && key_after(lo, t1, k)) t = t1;
+    else return false;
+    return true;
+}
+
 // ---- batch walk: implicit 8-ary range hierarchy + the reference batch test -----------------
 //
 // Level 0 is the reference's batch list (Model records, shader.comp:338); level L >= 1 node k
@@ -218,9 +249,10 @@ __device__ __forceinline__ bool node_hit(f3 o, f3 inv, const float4& lo, const f
 // MIN_EPSILON < t < max_dist sets `occluded` (shader.comp:379-396).  A hit batch's triangles
 // (v0, e1, e2: 48 B each) are staged through LDS 64 at a time by one coalesced load per
 // lane, then read back as wave-wide broadcasts.
-template <bool COUNT, bool SHADOW>
+template <bool COUNT, bool SHADOW, bool AFTER = false>
 __device__ __forceinline__ void walk_batches(const KArgs& A, f3 o, f3 d, f3 inv, Hit& h, bool& occluded,
-                                             float max_dist, Cnt& c, float4* slab) {
+                                             float max_dist, Cnt& c, float4* slab, const HitKey* lo = nullptr) {
+    static_assert(!AFTER || !SHADOW, "the lower bound serves the nearest-hit search");
     const uint32_t nb = A.nbatch, top = A.top;
     uint32_t s = 0, L = top, skip = 0;
     while (s < nb) {
@@ -299,6 +331,10 @@ __device__ __forceinline__ void walk_batches(const KArgs& A, f3 o, f3 d, f3 inv,
                                 break;
                             }
                         } else if (t > TRT_EPS && t < h.t) {
+                            if constexpr (AFTER) { // s is the batch: the key of this candidate
+                                if (!key_after(*lo, t, hit_key(2u, s, (uint32_t)(start + base + k)))) continue;
+                                h.batch = s;
+                            }
                             h.t = t;
                             h.kind = HIT_TRI;
                             h.idx = start + base + k;
@@ -451,9 +487,10 @@ __device__ __forceinline__ void leaf_range(uint32_t node, uint32_t& first, uint3
     n = ((node >> kBvhCountShift) & 15u) + 1u;
 }
 
-template <bool COUNT, bool SHADOW, int GEOM>
+template <bool COUNT, bool SHADOW, int GEOM, bool AFTER = false>
 __device__ __forceinline__ void trace_bvh(const KArgs& A, f3 o, f3 d, f3 inv, Hit& h, bool& occluded,
-                                          float max_dist, Cnt& c, float4* slab) {
+                                          float max_dist, Cnt& c, float4* slab, const HitKey* lo = nullptr) {
+    static_assert(!AFTER || !SHADOW, "the lower bound serves the nearest-hit search");
     using Stack = BvhStack<bvh_lds_entries<GEOM>(), GEOM == 2>;
     typename Stack::Mem stack_mem;
     Stack stack(slab, stack_mem);
@@ -518,6 +555,8 @@ __device__ __forceinline__ void trace_bvh(const KArgs& A, f3 o, f3 d, f3 inv, Hi
                     const bool better = t < best || (t == best && h.kind == HIT_TRI &&
                                                      (batch < h.batch || (batch == h.batch && (int)tri < h.idx)));
                     if (!better) continue;
+                    if constexpr (AFTER)
+                        if (!key_after(*lo, t, hit_key(2u, batch, tri))) continue;
                 }
                 const BatchRec rec = A.batches[batch]; // the reference's gate for this triangle
                 const bool pass = aabb_hit(o, gate_inv(d), rec.bmin, rec.bmax);
@@ -548,9 +587,10 @@ __device__ __forceinline__ void trace_bvh(const KArgs& A, f3 o, f3 d, f3 inv, Hi
 // Tests the leaf `node` (1-4 triangles of the BVH-ordered array).  SHADOW: returns true when
 // an accepted candidate occludes.  The next triangle's record is loaded before the current
 // one is tested (one exposed load latency per leaf instead of one per triangle).
-template <bool COUNT, bool SHADOW>
+template <bool COUNT, bool SHADOW, bool AFTER = false>
 __device__ __forceinline__ bool bvh_leaf(const KArgs& A, uint32_t node, f3 o, f3 d, f3 inv, Hit& h,
-                                         float max_dist, float& best, Cnt& c) {
+                                         float max_dist, float& best, Cnt& c, const HitKey* lo = nullptr) {
+    static_assert(!AFTER || !SHADOW, "the lower bound serves the nearest-hit search");
     uint32_t first, n;
     leaf_range(node, first, n);
 #ifndef TRT_LEAF_PREFETCH
@@ -587,6 +627,8 @@ __device__ __forceinline__ bool bvh_leaf(const KArgs& A, uint32_t node, f3 o, f3
             const bool better = t < best || (t == best && h.kind == HIT_TRI &&
                                              (batch < h.batch || (batch == h.batch && (int)tri < h.idx)));
             if (!better) continue;
+            if constexpr (AFTER)
+                if (!key_after(*lo, t, hit_key(2u, batch, tri))) continue;
         }
         const BatchRec rec = A.batches[batch]; // the reference's gate for this triangle
         const bool pass = aabb_hit(o, gate_inv(d), rec.bmin, rec.bmax);
@@ -819,9 +861,9 @@ __device__ __forceinline__ bool visit4q(f3 o, f3 inv, float best, const float4& 
 #endif
 template <int GEOM>
 constexpr bool g3_quant_only() { return GEOM == 3 && TRT_G3_QONLY && TRT_BVH_QUANT; }
-template <bool COUNT, bool SHADOW, int GEOM>
+template <bool COUNT, bool SHADOW, int GEOM, bool AFTER = false>
 __device__ __forceinline__ void trace_bvh4(const KArgs& A, f3 o, f3 d, f3 inv, Hit& h, bool& occluded,
-                                           float max_dist, Cnt& c, float4* slab) {
+                                           float max_dist, Cnt& c, float4* slab, const HitKey* lo = nullptr) {
     using Stack = BvhStack<bvh_lds_entries<GEOM>(), GEOM == 2>;
     typename Stack::Mem stack_mem;
     Stack stack(slab, stack_mem);
@@ -862,7 +904,7 @@ __device__ __forceinline__ void trace_bvh4(const KArgs& A, f3 o, f3 d, f3 inv, H
                 ++c.wn;
 #endif
                 if (visit4q<COUNT>(o, inv, best, pe, qa, qb, ch, stack, node, c)) continue;
-            } else if (bvh_leaf<COUNT, SHADOW>(A, node, o, d, inv, h, max_dist, best, c)) {
+            } else if (bvh_leaf<COUNT, SHADOW, AFTER>(A, node, o, d, inv, h, max_dist, best, c, lo)) {
                 occluded = true;
                 return;
             }
@@ -902,7 +944,7 @@ __device__ __forceinline__ void trace_bvh4(const KArgs& A, f3 o, f3 d, f3 inv, H
             ++c.wn;
 #endif
             if (visit4<COUNT>(o, inv, best, lx, ly, lz, hx, hy, hz, ch, stack, node, c)) continue;
-        } else if (bvh_leaf<COUNT, SHADOW>(A, node, o, d, inv, h, max_dist, best, c)) {
+        } else if (bvh_leaf<COUNT, SHADOW, AFTER>(A, node, o, d, inv, h, max_dist, best, c, lo)) {
             occluded = true;
             return;
         }
@@ -1027,22 +1069,34 @@ __device__ __forceinline__ bool floor_hit(f3 o, f3 d, float tmax, float& t) {
     return false;
 }
 
-template <bool COUNT, int GEOM>
-__device__ __forceinline__ void scene_intersect(const KArgs& A, f3 o, f3 d, Hit& h, Cnt& c, float4* slab) {
-    h.t = 1e10f;
+// AFTER (all_hits_kernel only): the nearest hit inside tmax whose key is strictly greater than lo.
+// Both roots of a sphere are candidates then, t0 first: the smaller one that passes is the sphere's
+// candidate of this search (equal roots share a key, so a tangent ray gives one hit).
+template <bool COUNT, int GEOM, bool AFTER = false>
+__device__ __forceinline__ void scene_intersect(const KArgs& A, f3 o, f3 d, Hit& h, Cnt& c, float4* slab,
+                                                float tmax = 1e10f, const HitKey* lo = nullptr) {
+    h.t = AFTER ? tmax : 1e10f;
     h.kind = HIT_NONE;
     h.idx = 0;
     h.u = 0.0f;
     h.v = 0.0f;
     h.ni = 0;
     h.batch = 0;
-    if ((A.flags & TRT_FLAG_FLOOR) && floor_hit(o, d, h.t, h.t)) h.kind = HIT_FLOOR;
+    if constexpr (AFTER) {
+        float tf; // the floor's key is the least of its t: it counts iff t > lo.t
+        if ((A.flags & TRT_FLAG_FLOOR) && floor_hit(o, d, h.t, tf) && tf > lo->t) {
+            h.t = tf;
+            h.kind = HIT_FLOOR;
+        }
+    } else if ((A.flags & TRT_FLAG_FLOOR) && floor_hit(o, d, h.t, h.t)) h.kind = HIT_FLOOR;
     if (A.flags & TRT_FLAG_SPHERES) { // shader.comp:322-335
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             float t = 1e10f;
             if (COUNT) ++c.sph;
-            const bool hit = sphere_hit(o, d, A.sph[i], t);
+            bool hit;
+            if constexpr (AFTER) hit = sphere_hit_after(o, d, A.sph[i], *lo, hit_key(1u, (uint32_t)i, 0u), t);
+            else hit = sphere_hit(o, d, A.sph[i], t);
             if (hit && t < h.t) {
                 h.t = t;
                 h.kind = HIT_SPHERE;
@@ -1055,10 +1109,10 @@ __device__ __forceinline__ void scene_intersect(const KArgs& A, f3 o, f3 d, Hit&
     f3 inv = GEOM >= 2 ? cull_inv(d) : mk(rcp_rn_lane(d.x), rcp_rn_lane(d.y), rcp_rn_lane(d.z)); // shader.comp:336
     bool unused = false;
     if (GEOM >= 2) {
-        if (g3_quant_only<GEOM>() || (TRT_BVH_WIDTH == 4 && A.bvh4)) trace_bvh4<COUNT, false, GEOM>(A, o, d, inv, h, unused, 0.0f, c, slab);
-        else trace_bvh<COUNT, false, GEOM>(A, o, d, inv, h, unused, 0.0f, c, slab);
+        if (g3_quant_only<GEOM>() || (TRT_BVH_WIDTH == 4 && A.bvh4)) trace_bvh4<COUNT, false, GEOM, AFTER>(A, o, d, inv, h, unused, 0.0f, c, slab, lo);
+        else trace_bvh<COUNT, false, GEOM, AFTER>(A, o, d, inv, h, unused, 0.0f, c, slab, lo);
     }
-    else walk_batches<COUNT, false>(A, o, d, inv, h, unused, 0.0f, c, slab);
+    else walk_batches<COUNT, false, AFTER>(A, o, d, inv, h, unused, 0.0f, c, slab, lo);
 }
 
 // shadow_intersect, shader.comp:364-399: any hit on spheres / triangles; floor excluded.
@@ -3334,6 +3388,86 @@ hipError_t launch_occlusion_query(const KArgs& A0, const float4* segs, uint32_t 
     const dim3 grid((n + 63u) / 64u), block(64);
     dispatch_geom(geom_of(A), [&](auto g) {
         hipLaunchKernelGGL(occlusion_query_kernel<decltype(g)::value>, grid, block, 0, stream, A, segs, n, out);
+    });
+    return hipGetLastError();
+}
+#endif
+
+// All-hits queries (abi.h trt_trace_all): one lane per caller segment, loaded and checked as
+// occlusion_query_kernel does.  A lane runs at most max_hits + 1 next-hit searches (a constant of
+// the launch bounds the loop): search j is scene_intersect with tmax for the initial nearest and
+// with the key of record j - 1 as a strict lower bound on the candidates' keys (HitKey, AFTER), so
+// it finds the next crossing in the order (t, class, a, b); a triangle that a spatial split
+// references twice, or a surface at the t just reported, cannot come again, and equal-t
+// neighbours come out in scene_intersect's tie order.  Box culling is unchanged (on the nearest so
+// far only).  RECORDS: each record goes straight to its slot as ray_query_kernel stores it (two
+// 16-byte stores, resolve_hit's normal); nothing per hit is kept.  A search that finds nothing ends
+// the lane; after max_hits records one more search decides TRT_ALLHITS_MORE.  Slots past the count
+// get the miss record, every slot of a bad record TRT_HIT_BAD_RAY.
+// Lanes that are done leave the loop while their wave-mates search on: the walks take any subset of
+// the wave, as occlusion_query_kernel explains (wave-uniform values from the first active lane,
+// ballots over the active lanes, one wave per workgroup at the LDS barriers).
+template <int GEOM, bool RECORDS>
+__global__ __launch_bounds__(64, waves_per_simd<GEOM>()) void all_hits_kernel(
+    KArgs A, const float4* __restrict__ segs, uint32_t n, uint32_t max_hits, uint4* __restrict__ hits,
+    uint32_t* __restrict__ counts) {
+    __shared__ float4 slab[slab_float4s<GEOM>()];
+    const uint32_t i = blockIdx.x * 64u + threadIdx.x;
+    if (i >= n) return;
+    const float4 a = segs[2 * (size_t)i], b = segs[2 * (size_t)i + 1];
+    const float tmax = a.w;
+    uint4* const rec = RECORDS ? hits + 2 * (size_t)i * max_hits : nullptr;
+    uint32_t m = 0u, r = TRT_ALLHITS_BAD_SEG;
+    uint4 fill = make_uint4(0u, TRT_HIT_BAD_RAY, 0u, 0u);
+    if (qseg_valid(a.x, a.y, a.z, b.x, b.y, b.z, tmax)) {
+        const f3 o = mk(a.x, a.y, a.z);
+        const f3 d = normalize3(mk(b.x, b.y, b.z)); // shader.comp:593
+        HitKey lo;
+        bool more = false;
+        for (uint32_t j = 0u; j <= max_hits; ++j) {
+            Hit h;
+            Cnt none;
+            scene_intersect<false, GEOM, true>(A, o, d, h, none, slab, tmax, &lo);
+            if (h.kind == HIT_NONE) break;
+            if (j == max_hits) {
+                more = true;
+                break;
+            }
+            if constexpr (RECORDS) {
+                const f3 nn = resolve_hit<false>(A, Seg{o, d, 1.0f, 0}, h, none).n;
+                rec[2 * j] = make_uint4(__float_as_uint(h.t), (uint32_t)h.kind, (uint32_t)h.idx, __float_as_uint(h.u));
+                rec[2 * j + 1] =
+                    make_uint4(__float_as_uint(h.v), __float_as_uint(nn.x), __float_as_uint(nn.y), __float_as_uint(nn.z));
+            }
+            lo.t = h.t;
+            lo.k = h.kind == HIT_FLOOR    ? hit_key(0u, 0u, 0u)
+                   : h.kind == HIT_SPHERE ? hit_key(1u, (uint32_t)h.idx, 0u)
+                                          : hit_key(2u, h.batch, (uint32_t)h.idx);
+            m = j + 1u;
+        }
+        r = m | (more ? TRT_ALLHITS_MORE : 0u);
+        fill = make_uint4(__float_as_uint(1e10f), (uint32_t)HIT_NONE, 0u, 0u);
+    }
+    counts[i] = r;
+    if constexpr (RECORDS)
+        for (uint32_t j = m; j < max_hits; ++j) {
+            rec[2 * j] = fill;
+            rec[2 * j + 1] = make_uint4(0u, 0u, 0u, 0u);
+        }
+}
+
+#ifndef TRT_KRES_ONLY
+hipError_t launch_all_hits(const KArgs& A0, const float4* segs, uint32_t n, uint32_t max_hits, uint4* hits,
+                           uint32_t* counts, hipStream_t stream) {
+    if (!n) return hipSuccess;
+    if (max_hits < 1u || max_hits > TRT_ALLHITS_MAX) return hipErrorInvalidValue;
+    KArgs A = A0;
+    A.diag = nullptr;
+    const dim3 grid((n + 63u) / 64u), block(64);
+    dispatch_geom(geom_of(A), [&](auto g) {
+        constexpr int G = decltype(g)::value;
+        if (hits) hipLaunchKernelGGL((all_hits_kernel<G, true>), grid, block, 0, stream, A, segs, n, max_hits, hits, counts);
+        else hipLaunchKernelGGL((all_hits_kernel<G, false>), grid, block, 0, stream, A, segs, n, max_hits, hits, counts);
     });
     return hipGetLastError();
 }

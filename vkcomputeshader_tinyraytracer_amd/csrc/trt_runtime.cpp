@@ -1563,6 +1563,58 @@ int trt_visibility(trt_ctx* c, const trt_params* p, const trt_qpoint* pts, uint3
     return finish_call(c, dev, false, timing, st, {{out, d_out, n * sizeof(uint64_t)}});
 }
 
+// All-hits queries (abi.h): the caller's segments through all_hits_kernel, up to max_hits records
+// and one count each.  Shaped like trt_occluded; host segments stage through the ray-query record
+// buffer, the records through the hit-record buffer and the counts through the RGBA8 buffer.
+int trt_trace_all(trt_ctx* c, const trt_params* p, const trt_qseg* segs, uint32_t nsegs, uint32_t max_hits, trt_qhit* hits,
+                  uint32_t* counts, trt_stats* st) {
+    if (!c) return TRT_ERR_INVALID;
+    if (!p) return fail(c, TRT_ERR_INVALID, "trt_trace_all: null params");
+    if (!c->have_scene) return fail(c, TRT_ERR_NOSCENE, "trt_trace_all: no scene uploaded");
+    if (p->flags & TRT_FLAG_COUNT) return fail(c, TRT_ERR_INVALID, "trt_trace_all: TRT_FLAG_COUNT is not offered");
+    if ((p->flags & TRT_FLAG_TIMING) && !st) return fail(c, TRT_ERR_INVALID, "trt_trace_all: TRT_FLAG_TIMING needs stats");
+    if (max_hits < 1u || max_hits > TRT_ALLHITS_MAX) return fail(c, TRT_ERR_INVALID, "trt_trace_all: max_hits must be 1..32");
+    if ((uint64_t)nsegs * max_hits > TRT_QRAY_MAX_RAYS) return fail(c, TRT_ERR_INVALID, "trt_trace_all: more than 2^28 hit slots");
+    if (nsegs && !segs) return fail(c, TRT_ERR_INVALID, "trt_trace_all: null segs");
+    if (nsegs && !counts) return fail(c, TRT_ERR_INVALID, "trt_trace_all: null counts");
+    const bool dev = (p->flags & TRT_FLAG_DEVICE_PTRS) != 0;
+    // the kernel moves a segment and a hit record as 16-byte vectors and a count as one word,
+    // straight from and to the caller's device arrays (host arrays are staged)
+    if (dev && ((reinterpret_cast<uintptr_t>(segs) | reinterpret_cast<uintptr_t>(hits)) & 15u))
+        return fail(c, TRT_ERR_INVALID, "trt_trace_all: device segs and hits must be 16-byte aligned");
+    if (dev && (reinterpret_cast<uintptr_t>(counts) & 3u))
+        return fail(c, TRT_ERR_INVALID, "trt_trace_all: device counts must be 4-byte aligned");
+    const bool timing = (p->flags & TRT_FLAG_TIMING) != 0;
+    if (st) std::memset(st, 0, sizeof(*st));
+    if (nsegs == 0) return TRT_OK;
+    if (!dev) { // a device array cannot be read here: the kernel applies the same predicate
+        uint32_t bad = 0;
+        if (trt_check_segs(segs, nsegs, &bad) != TRT_OK)
+            return fail(c, TRT_ERR_INVALID, "trt_trace_all: segment " + std::to_string(bad) +
+                                                " is not valid (non-finite, direction length or tmax out of range)");
+    }
+    HIP_TRY(c, hipSetDevice(c->device));
+
+    const trt_params q = query_params(p, 1, TRT_FLAG_SPHERES | TRT_FLAG_FLOOR | TRT_FLAG_BATCH_WALK | TRT_FLAG_DEVICE_PTRS | TRT_FLAG_TIMING);
+    int rc;
+    KArgs A;
+    fill_args(c, &q, A);
+    A.view_on = 0;
+
+    const float4* d_segs = reinterpret_cast<const float4*>(segs);
+    uint4* dh = reinterpret_cast<uint4*>(hits);
+    uint32_t* d_counts = counts;
+    const size_t n = nsegs, nh = n * max_hits;
+    if (!dev) {
+        if ((rc = stage(c, &c->d_qrays, &c->capqrays, n * sizeof(trt_qseg), "alloc query segments", segs, &d_segs)) != TRT_OK) return rc;
+        if (hits && (rc = stage(c, &c->d_qhits, &c->capqhits, nh * sizeof(trt_qhit), "alloc all-hits records", nullptr, &dh)) != TRT_OK) return rc;
+        if ((rc = stage(c, &c->d_out8, &c->cap8, n * sizeof(uint32_t), "alloc all-hits counts", nullptr, &d_counts)) != TRT_OK) return rc;
+    }
+    if ((rc = begin_call(c, false, timing)) != TRT_OK) return rc;
+    HIP_TRY(c, trt::launch_all_hits(A, d_segs, nsegs, max_hits, dh, d_counts, c->stream));
+    return finish_call(c, dev, false, timing, st, {{hits, dh, nh * sizeof(trt_qhit)}, {counts, d_counts, n * sizeof(uint32_t)}});
+}
+
 } // extern "C"
 
 // ---- envmap JPEG: host entropy decode + GPU reconstruction ----------------

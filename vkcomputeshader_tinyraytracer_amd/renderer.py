@@ -302,6 +302,93 @@ class Renderer:
         self._check(self._L.trt_occluded(self._h, ctypes.byref(p), ptrs[0], n, ptrs[1], ctypes.byref(st)))
         return (out, st.as_dict()) if timing else out
 
+    # -- all-hits queries --------------------------------------------------------------------
+    def trace_all(self, segs, params: T.Params, max_hits: int = 8, *, want_hits: bool = True, hits=None, counts=None,
+                  timing: bool = False, nsegs: int | None = None):
+        """Every surface crossing of the caller's segments, nearest first (trt_trace_all): up to
+        `max_hits` (1..T.ALLHITS_MAX) T.QHIT records per segment in the order (t, floor < sphere <
+        triangle, index), and a count.  counts[i] & 0x7fffffff is the number of records, bit
+        T.ALLHITS_MORE says further hits exist inside tmax; slots past the count hold the miss
+        record.  `segs`, the flags of `params` and the host / device conventions are those of
+        `occluded`: a numpy array of T.QSEG (validated first; a bad one raises TrtError and leaves
+        the outputs untouched) or a contiguous torch CUDA tensor (16-byte aligned, only enqueued
+        unless timing; a segment that is not valid reads T.ALLHITS_BAD_SEG and kind T.HIT_BAD_RAY
+        in every slot).  Outputs are made on the side of the segments unless given and may be
+        longer than the query; on the device hits are an (n, K, 32) uint8 tensor and counts
+        torch.int32 (the same bits).  With want_hits false (and no `hits`) only the counts are
+        produced; max_hits still bounds them.
+        Returns (hits (n, K) or None, counts (n,) uint32), with `timing` also the stats_dict."""
+        p = T.Params.from_buffer_copy(params)
+        p.rays_in = None
+        K = int(max_hits)
+        if _is_torch_cuda(segs):
+            import torch
+
+            if not segs.is_contiguous():
+                raise ValueError("segs must be a contiguous device tensor of T.QSEG records")
+            have = segs.numel() * segs.element_size() // T.QSEG.itemsize
+            n = have if nsegs is None else int(nsegs)
+            if n > have:
+                raise ValueError(f"{n} segments asked of a tensor that holds {have}")
+            p.flags |= T.FLAG_DEVICE_PTRS
+            if hits is None and want_hits:
+                hits = torch.empty((n, max(K, 0), T.QHIT.itemsize), dtype=torch.uint8, device=segs.device)
+            if counts is None:
+                counts = torch.empty((n,), dtype=torch.int32, device=segs.device)
+            for x, need in ((hits, n * K * T.QHIT.itemsize), (counts, n * 4)):
+                if x is not None and not (_is_torch_cuda(x) and x.is_contiguous() and x.numel() * x.element_size() >= need):
+                    raise ValueError("outputs of a device query are contiguous device tensors that hold every segment")
+            ptrs = (segs.data_ptr(), None if hits is None else hits.data_ptr(), counts.data_ptr())
+        else:
+            p.flags &= ~T.FLAG_DEVICE_PTRS
+            s = None if segs is None else np.ascontiguousarray(segs, T.QSEG).reshape(-1)
+            n = (0 if s is None else s.shape[0]) if nsegs is None else int(nsegs)
+            if s is not None and n > s.shape[0]:
+                raise ValueError(f"{n} segments asked of an array that holds {s.shape[0]}")
+            if hits is None and want_hits:
+                hits = np.empty((n, max(K, 0)), T.QHIT)
+            if counts is None:
+                counts = np.empty((n,), np.uint32)
+            for x, dtype, need in ((hits, T.QHIT, n * K), (counts, np.uint32, n)):
+                if x is not None and not (isinstance(x, np.ndarray) and x.flags["C_CONTIGUOUS"] and x.dtype == dtype
+                                          and x.size >= need):
+                    raise ValueError("outputs of a host query are C-contiguous numpy arrays that hold every segment")
+            ptrs = (None if s is None or not len(s) else s.ctypes.data, None if hits is None else hits.ctypes.data,
+                    counts.ctypes.data)
+        if timing:
+            p.flags |= T.FLAG_TIMING
+        else:
+            p.flags &= ~T.FLAG_TIMING
+        st = T.Stats()
+        self._check(self._L.trt_trace_all(self._h, ctypes.byref(p), ptrs[0], n, K & 0xFFFFFFFF, ptrs[1], ptrs[2],
+                                          ctypes.byref(st)))
+        return (hits, counts, st.as_dict()) if timing else (hits, counts)
+
+    def contains(self, points, params: T.Params, direction=(0.3, 1.0, 0.2)) -> np.ndarray:
+        """Which of the (n, 3) host `points` lie inside the scene's closed meshes: one whole-ray,
+        count-only `trace_all` per point along `direction`, with the floor and the spheres cleared;
+        inside means an odd number of crossings.  Raises if any ray crosses more than
+        T.ALLHITS_MAX surfaces.  The usual caveat of parity tests applies: a ray through an edge or
+        a vertex shared by two triangles may count that crossing twice or not at all (the
+        Moller-Trumbore test is inclusive on the edges), a ray grazing a surface tangentially
+        counts a touch as a crossing, and an open or self-intersecting mesh has no inside; choose
+        a direction that is not aligned with the mesh, or vote over several.
+        Returns an (n,) bool array."""
+        from .scene import crossing_parity
+
+        pts = np.ascontiguousarray(points, np.float32).reshape(-1, 3)
+        segs = np.zeros(len(pts), T.QSEG)
+        segs["org"] = pts
+        segs["dir"] = np.asarray(direction, np.float32)
+        segs["tmax"] = T.QSEG_MAX_T
+        p = T.Params.from_buffer_copy(params)
+        p.flags &= ~(T.FLAG_FLOOR | T.FLAG_SPHERES)
+        _, counts = self.trace_all(segs, p, T.ALLHITS_MAX, want_hits=False)
+        odd, truncated = crossing_parity(counts)
+        if truncated.any():
+            raise ValueError(f"contains: {int(truncated.sum())} rays cross more than {T.ALLHITS_MAX} surfaces")
+        return odd
+
     # -- visibility masks --------------------------------------------------------------------
     def visibility(self, points, params: T.Params, *, dirs=None, targets=None, out=None, timing: bool = False,
                    npoints: int | None = None):

@@ -283,6 +283,35 @@ def point_segments(points, dirs=None, targets=None) -> np.ndarray:
     return out
 
 
+def inside_length(hits, counts) -> np.ndarray:
+    """The length each segment of a Renderer.trace_all answer spends inside closed meshes: its
+    triangle records, in order, are paired (first with second, third with fourth, ...) and the
+    differences of t summed, in float64; an unpaired last crossing adds nothing.  Floor and sphere
+    records are left out.  Meaningful for origins outside the meshes (a segment that starts
+    inside pairs its exit with the next entry) and for answers that are not truncated
+    (crossing_parity).  `hits` is (n, K) T.QHIT, `counts` (n,); returns (n,) float64."""
+    h = np.asarray(hits, T.QHIT)
+    c = np.asarray(counts).astype(np.uint32).reshape(-1)
+    if h.ndim != 2 or h.shape[0] != len(c):
+        raise ValueError("hits are (n, K) T.QHIT records and counts (n,)")
+    m = np.where(c == T.ALLHITS_BAD_SEG, 0, c & 0x7FFFFFFF)
+    tri = (np.arange(h.shape[1])[None, :] < m[:, None]) & (h["kind"] == T.HIT_TRIANGLE)
+    rank = np.cumsum(tri, 1) - 1  # the index of a triangle record among its segment's
+    ntri = tri.sum(1)
+    paired = tri & (rank < (ntri - ntri % 2)[:, None])
+    sign = np.where(rank % 2 == 1, 1.0, -1.0)
+    return np.where(paired, sign * h["t"].astype(np.float64), 0.0).sum(1)
+
+
+def crossing_parity(counts) -> tuple[np.ndarray, np.ndarray]:
+    """(odd, truncated) of a Renderer.trace_all count array: whether the number of crossings is
+    odd (a point inside a closed mesh, for a whole ray from it), and whether the count carries
+    T.ALLHITS_MORE, in which case the parity is that of max_hits and says nothing.  A bad record
+    (T.ALLHITS_BAD_SEG) is reported as truncated."""
+    c = np.asarray(counts).astype(np.uint32)
+    return (c & 1).astype(bool) & (c != T.ALLHITS_BAD_SEG), (c & T.ALLHITS_MORE) != 0
+
+
 def camera_orbit(ubo: np.ndarray, n: int, speed: float = 0.02, yaw_step: float = 1.0, pitch_step: float = -0.25,
                  yaw0: float = 0.0, pitch0: float = 0.0) -> tuple[np.ndarray, np.ndarray]:
     """camera_path with a camera that turns while it walks (mouse look held with W and D): n

@@ -65,6 +65,10 @@ OCC_OCCLUDED = 1
 OCC_BAD_SEG = 0xFF  # a device-pointer query's byte for a segment that is not valid
 QSEG_MAX_T = np.float32(1e10)  # TRT_QSEG_MAX_T: the shader's initial nearest distance, "a whole ray"
 assert QSEG.itemsize == 32
+# abi.h trt_trace_all: every crossing of a segment, in order (Renderer.trace_all)
+ALLHITS_MAX = 32  # max_hits in 1..32
+ALLHITS_MORE = 0x80000000  # in counts[i]: further hits exist inside tmax
+ALLHITS_BAD_SEG = 0xFFFFFFFF  # a device-pointer query's count for a segment that is not valid
 # abi.h trt_qpoint: a point of a visibility query (Renderer.visibility); n only chooses the side
 # of a TRT_VIS_DIRS direction, tmax cuts a direction off and caps the range to a target
 QPOINT = np.dtype([("pos", "<f4", (3,)), ("tmax", "<f4"), ("n", "<f4", (3,)), ("pad", "<f4")])
